@@ -29,6 +29,11 @@ memory both buffers and three more allocations of the process are on (vhp_probe_
 
 The defaults (100 steps after 10 warm-up launches, ~0.1 s of GPU time) report the sustained rate.
 
+`--dump-outputs DIR` writes what the main timed region's last step left for its caller as DIR/<name>.npy (float64, or float32
+for --dtype f32; at most 64 MB in all): for the sweep a fixed, seeded sample of the fields (whole fields by source index and
+single cells drawn from the whole batch, sample_fields), for --workload c4 the planner's device results.  The inputs of a
+workload are seeded, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
 import argparse
@@ -44,13 +49,61 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 BYTES_PER_CELL = {"f64": 9, "f32": 5}  # 1 B occupancy read + sizeof(field element) written
+DUMP_BYTES = 64 << 20          # --dump-outputs: everything written, at most
+DUMP_FIELD_BYTES = 40 << 20    # ... of which whole fields
+DUMP_CELLS = 1 << 20           # ... and this many single cells (+ their float64 indices)
+DUMP_SEED = 20240605
+
+
+def sample_fields(fields, seed=DUMP_SEED):
+    """--dump-outputs: a fixed, seeded sample of a batch of fields (torch tensor [n, ny, nx], any device) that fits DUMP_BYTES --
+    as many whole fields as fit in DUMP_FIELD_BYTES, chosen by index, and DUMP_CELLS single cells drawn from the whole batch --
+    as numpy arrays of the fields' dtype, with the indices as float64.  The same shape and seed always pick the same cells."""
+    import numpy as np
+    import torch
+    n = int(fields.shape[0])
+    per = int(fields[0].numel())
+    rs = np.random.RandomState(seed)
+    pick = np.sort(rs.choice(n, min(n, DUMP_FIELD_BYTES // (per * fields.element_size())), replace=False))
+    cells = np.sort(rs.randint(0, n * per, size=min(DUMP_CELLS, n * per), dtype=np.int64))
+    flat = fields.reshape(-1)
+    return {"fields": fields[torch.from_numpy(pick).to(fields.device)].cpu().numpy(),
+            "fields_source_index": pick.astype(np.float64),
+            "cells": flat[torch.from_numpy(cells).to(fields.device)].cpu().numpy(),
+            "cells_flat_index": cells.astype(np.float64)}
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy; float32 and float64 stay as they are, anything else (labels,
+    pivots) becomes float64 (exact: the values are below 2**53).  At most DUMP_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a if np.asarray(a).dtype in (np.float32, np.float64) else np.asarray(a, np.float64))
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(k + ".npy" for k in arrays)
+
+
+def hip_memcpy(dst, src, n_bytes, kind):
+    """hipMemcpy through the HIP runtime torch has loaded (kind 2: device to host, 3: device to device)."""
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    rc = hip.hipMemcpy(dst, src, n_bytes, kind)
+    if rc != 0:
+        raise RuntimeError("hipMemcpy failed: %d" % rc)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see the module docstring)")
     ap.add_argument("--workload", default="c3", choices=["c2", "c3", "c4", "c5", "c1-batch", "c-250", "c3-8", "c3-32", "c3-64", "c3-96", "c1k-empty", "c3-1024", "c3-1016", "c3-512"],
                     help="c3 (default): BASELINE config 3, the configuration the metric is quoted on; c2 / c4 / c5: configs 2, 4, 5 (per-GPU share); "
                          "c1-batch: the reference's own headline size -- config 1's 101x101 rnd_1 mask -- as a batch of 4096 sources; c-250: a 250x250 "
@@ -88,7 +141,10 @@ def parse():
                          "place of the sweep (no GPU, no library): for the CPU test of `bench.py --gpus N`; never a result")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def make_workload(name, rank, n_src):
@@ -216,10 +272,21 @@ def bench_planner(args):
     dev_ms = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ctx.planner_solve_device(start, end, 0.1, 250)
+        last = ctx.planner_solve_device(start, end, 0.1, 250)
         dev_ms.append(ctx.last_elapsed_ms())
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:   # the last solve's device results (valid until the next solve: the speculative runs below)
+        rc, n_last, ptrs = last
+        res = {"status": np.array([rc], np.float64)}
+        if ptrs:
+            for name, dt, shape in (("labels", np.uint32, (ny, nx)), ("vis_global", np.float64, (ny, nx)),
+                                    ("vis_local", np.float64, (ny, nx)), ("pivots", np.int32, (n_last + 1, 2))):
+                a = np.empty(shape, dt)
+                hip_memcpy(a.ctypes.data, ptrs[name], a.nbytes, 2)
+                res[name] = a
+        dumped = write_outputs(args.dump_outputs, res)
     loop_ms = float(np.mean(dev_ms))
     bytes_per_pivot = 32 * nx * ny  # vis_local 8 W + 8 R, vis_global 8 R + 8 W, labels 4 R + 4 W
     achieved = bytes_per_pivot * n_piv / (loop_ms * 1e-3) / 1e9
@@ -228,7 +295,8 @@ def bench_planner(args):
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "reference fixture (images/maze_6.png as tests/golden/maze_6.npz)",
         "config": {"workload": "C4: maze_6, start {345,391}, end {341,10}, visibilityThreshold 0.1: %d pivots per solve, results device-resident" % n_piv,
-                   "us_per_pivot_device_loop": round(loop_ms * 1e3 / n_piv, 2), "us_per_pivot_wall": round(elapsed / args.steps * 1e6 / n_piv, 2)},
+                   "us_per_pivot_device_loop": round(loop_ms * 1e3 / n_piv, 2), "us_per_pivot_wall": round(elapsed / args.steps * 1e6 / n_piv, 2),
+                   "dump_outputs": dumped},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                      "traffic": None, "kernel": "sweep of the iteration (vhp_lat_sweep where a batch of one takes it, else vhp_planner_sweep) + vhp_planner_epilogue", "kernel_ms": round(loop_ms, 4),
                      "note": "latency case by construction: one source per pivot, pivots are sequential (SURVEY 8d expectation management)"},
@@ -313,9 +381,10 @@ def bench_dry_run(args, rank, world):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        work.sum()
+        last = work.sum()
     barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
+    dumped = write_outputs(args.dump_outputs, {"stub_sum": np.array([last])}) if args.dump_outputs and rank == 0 else None
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     with_coll = None
@@ -340,7 +409,8 @@ def bench_dry_run(args, rank, world):
                           "ms_per_step": round(float(t.item()) / args.steps * 1e3, 4), "higher_is_better": True,
                           "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                           "dry_run": True, "config": {"workload": "DRY RUN: CPU stub, no sweep", "sources_per_gpu": n_src,
-                                                       "sharding": "sources/%d" % world, "backend": args.backend}}), flush=True)
+                                                       "sharding": "sources/%d" % world, "backend": args.backend,
+                                                       "dump_outputs": dumped}}), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -513,6 +583,12 @@ def main():
         return float(t.item()), float(k.sum()) / steps
 
     elapsed, kern_ms = timed_region()
+    # --dump-outputs: sampled here, before any other launch writes a result buffer; written to disk behind everything
+    dump = None
+    if args.dump_outputs and rank == 0:
+        if gathered is None and d_out is not d_first:   # the library-placed buffer (a raw pointer): into the first allocation,
+            hip_memcpy(d_first.data_ptr(), d_out.data_ptr(), out_bytes, 3)   # which the region behind this one rewrites anyway
+        dump = sample_fields(gathered if gathered is not None else d_first)   # (a step with the all-gather: what its caller receives)
     # the same K steps into the OTHER result buffer (the library-placed one, or with --output-buffer placed the first allocation)
     other = None
     if d_other is not None:
@@ -645,6 +721,7 @@ def main():
                 traffic_src = "static: %s (rocprofv3 --pmc passes of this command, not measured in this run)" % os.path.relpath(tpath, ROOT)
             except Exception:
                 traffic = None
+        dumped = write_outputs(args.dump_outputs, dump) if dump is not None else None
         out = {
             "metric": "visibility fields/sec on %dx%d grid" % (nx, ny),
             "value": round(fields / elapsed, 2),
@@ -664,6 +741,7 @@ def main():
             "config": {"workload": label, "grid": [nx, ny], "sources_per_gpu": n_src, "sharding": "sources/%d" % world,
                        "kernel_option": args.kernel,
                        "self_check": self_check,
+                       "dump_outputs": dumped,
                        "output_placement": placement,
                        "collective": ("rccl all_gather of fields (%s%s)" % (args.gather_mode if gathered is not None else "", ", %d chunks per shard" % args.chunks if overlapped else "")
                                       if gathered is not None else "none (independent sources)"),

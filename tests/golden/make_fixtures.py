@@ -1,7 +1,9 @@
-"""Generates tests/golden/*.npz from DATA the reference ships (never from its code).
+"""Generates tests/golden/*.npz from DATA the reference ships (never from its code), and ref_parser.json from what the
+reference's parser, built into oracle/_ref, returns and prints.
 
 Run in the build container only (needs /root/reference and Pillow):
     python tests/golden/make_fixtures.py
+    python tests/golden/make_fixtures.py ref_parser      (maze_6.png, settings.config and ref_parser.json only)
 
 maze_6.npz : images/maze_6.png reduced exactly as the reference's loadImage does
              (src/environment.cpp:195-203: free <=> red channel == 255; field(x,y) =
@@ -26,8 +28,17 @@ samples_1000.npz : the reference's own published outputs of this path, Samples/S
              are (image orientation), the source, the ball radius; synth.samples_1000() derives the occupancy and
              the grey planes.  Cells whose value the images show = y >= 1, not blocked, farther than 16 from the
              source (951 360 of them).
+maze_6.png / settings.config : images/maze_6.png and config/settings.config as the reference ships them (byte for byte),
+             the inputs of the host-surface tests' image loader and parser.
+ref_parser.json : what the reference's own ConfigParser (oracle/_ref/libref_parser.so, `make -C oracle ref`) returns and
+             prints for every config text of tests/test_host_surface.py::CONFIGS and for settings.config: parse()'s
+             result, the Config fields and the bytes written to stdout and stderr.
 """
+import json
 import os
+import shutil
+import sys
+import tempfile
 
 import numpy as np
 from PIL import Image
@@ -48,6 +59,53 @@ def main():
     np.savez_compressed(os.path.join(OUT, "c1_rnd1_mask.npz"), packed=np.packbits(c1, axis=1), nx=c1.shape[1], ny=c1.shape[0])
     print("c1_rnd1_mask", c1.shape, "free cells", int(c1.sum()))
     samples_1000()
+    ref_parser()
+
+
+def _captured(fn):
+    """fn()'s result and what it wrote to file descriptors 1 and 2 (C++ streams included)."""
+    import ctypes
+    libc = ctypes.CDLL(None)
+    sys.stdout.flush()
+    sys.stderr.flush()
+    saved = [os.dup(1), os.dup(2)]
+    with tempfile.TemporaryFile() as out, tempfile.TemporaryFile() as err:
+        os.dup2(out.fileno(), 1)
+        os.dup2(err.fileno(), 2)
+        try:
+            r = fn()
+            libc.fflush(None)
+        finally:
+            os.dup2(saved[0], 1)
+            os.dup2(saved[1], 2)
+            os.close(saved[0])
+            os.close(saved[1])
+        out.seek(0)
+        err.seek(0)
+        return r, out.read().decode(), err.read().decode()
+
+
+def ref_parser():
+    tests = os.path.dirname(OUT)
+    sys.path[:0] = [tests, os.path.dirname(tests)]
+    import host_lib
+    from test_host_surface import CONFIGS
+    shutil.copyfile(os.path.join(REF, "images", "maze_6.png"), os.path.join(OUT, "maze_6.png"))
+    shutil.copyfile(os.path.join(REF, "config", "settings.config"), os.path.join(OUT, "settings.config"))
+    assert os.path.exists(host_lib.REF_PARSER), "build oracle/_ref first: make -C oracle ref"
+    texts = dict(CONFIGS, **{"settings.config": open(os.path.join(OUT, "settings.config")).read()})
+    rec = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, text in sorted(texts.items()):
+            path = os.path.join(d, "settings.config")
+            with open(path, "wb") as f:
+                f.write(text.encode())
+            (ok, cfg), out, err = _captured(lambda: host_lib.parse_config_reference(path))
+            rec[name] = {"text": text, "ok": ok, "config": cfg, "stdout": out, "stderr": err}
+    with open(os.path.join(OUT, "ref_parser.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("ref_parser:", len(rec), "configs")
 
 
 def samples_1000():
@@ -101,4 +159,7 @@ def c1_mask_from_rnd1(n=101):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_parser"]:
+        ref_parser()
+    else:
+        main()

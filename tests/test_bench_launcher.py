@@ -67,3 +67,41 @@ def test_bench_workloads_are_the_tested_launches():
     # other ranks sweep other sources of the same map
     occ1, src1, _ = bench.make_workload("c3", 1, 0)
     assert np.array_equal(occ1, maps.config_c3(1)[0]) and not np.array_equal(np.asarray(src1), np.asarray(maps.config_c3(256)[1]))
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    # --dump-outputs: the sample of a batch of fields is the same from run to run, holds what the batch holds at the indices it
+    # names, and stays within the 64 MB bound for C3's 256 fields of 1000 x 1000 doubles (a stand-in batch of that shape)
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    fields = torch.arange(256 * 1000 * 1000, dtype=torch.float64).reshape(256, 1000, 1000)
+    a, b = bench.sample_fields(fields), bench.sample_fields(fields)
+    assert sorted(a) == ["cells", "cells_flat_index", "fields", "fields_source_index"]
+    for k in a:
+        assert np.array_equal(a[k], b[k])
+    assert a["fields"].dtype == np.float64 and a["fields"].shape[1:] == (1000, 1000) and len(a["fields"]) >= 1
+    assert np.array_equal(a["fields"], fields.numpy()[a["fields_source_index"].astype(np.int64)])
+    assert np.array_equal(a["cells"], fields.numpy().reshape(-1)[a["cells_flat_index"].astype(np.int64)])
+    names = bench.write_outputs(str(tmp_path / "d"), a)
+    assert sum(os.path.getsize(tmp_path / "d" / n) for n in names) <= 64 << 20
+    assert bench.sample_fields(fields.float())["fields"].dtype == np.float32
+    lab = bench.write_outputs(str(tmp_path / "l"), {"labels": np.array([[0, 0xFFFFFFFF]], np.uint32)})
+    assert lab == ["labels.npy"] and np.load(tmp_path / "l" / "labels.npy").tolist() == [[0.0, 4294967295.0]]
+
+
+def test_dump_outputs_and_steps_on_the_command_line(tmp_path):
+    r = _run("--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "0", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_lines(r.stdout)[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["dump_outputs"] == ["stub_sum.npy"]
+    assert (tmp_path / "out" / "stub_sum.npy").exists()
+    assert _run("--gpus", "1", "--dry-run", "--steps", "0").returncode != 0

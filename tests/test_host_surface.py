@@ -1,6 +1,8 @@
 """Host-side surface: settings.config grammar, environment generator / image loader, text writers.
-CPU only.  The parser is compared field by field with the REFERENCE's own parser where
-oracle/_ref has been built (this container); the generator with the oracle restatement."""
+CPU only.  The parser is compared field by field with what the REFERENCE's own parser returns and prints, as recorded in
+tests/golden/ref_parser.json (and with the parser itself where oracle/_ref has been built); the generator with the oracle
+restatement."""
+import json
 import os
 import subprocess
 
@@ -33,30 +35,41 @@ def host():
     return host_lib.load()
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _reference_parse(path, name, capfd):
+    """What the REFERENCE's own parser returns and prints for the config file `path` (stored under the name `name`):
+    tests/golden/ref_parser.json (tests/golden/make_fixtures.py), checked against oracle/_ref where that has been built."""
+    with open(os.path.join(GOLDEN, "ref_parser.json")) as f:
+        rec = json.load(f)[name]
+    assert rec["text"].encode() == open(path, "rb").read(), "tests/golden/ref_parser.json is stale for %r" % name
+    want = (rec["ok"], rec["config"]), rec["stdout"], rec["stderr"]
+    live = host_lib.parse_config_reference(path)
+    if live is not None:
+        theirs = capfd.readouterr()
+        assert (live, theirs.out, theirs.err) == want
+    return want
+
+
 @pytest.mark.parametrize("name", sorted(CONFIGS))
 def test_parser_matches_reference(host, tmp_path, name, capfd):
     path = tmp_path / "settings.config"
     path.write_bytes(CONFIGS[name].encode())
     ok, cfg = host_lib.parse_config(host, str(path))
     mine = capfd.readouterr()
-    ref = host_lib.parse_config_reference(str(path))
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    theirs = capfd.readouterr()
+    ref, out, err = _reference_parse(str(path), name, capfd)
     assert (ok, cfg) == ref
-    assert mine.err == theirs.err and mine.out == theirs.out  # same diagnostics, same banner
+    assert mine.err == err and mine.out == out  # same diagnostics, same banner
 
 
 def test_parser_shipped_file(host, capfd):
-    path = "/root/reference/config/settings.config"
-    if not os.path.exists(path):
-        pytest.skip("reference tree absent")
+    path = os.path.join(GOLDEN, "settings.config")   # config/settings.config as the reference ships it
     got = host_lib.parse_config(host, path)
     mine = capfd.readouterr()
-    ref = host_lib.parse_config_reference(path)
-    theirs = capfd.readouterr()
+    ref, out, _ = _reference_parse(path, "settings.config", capfd)
     assert got == ref and got[0] and got[1]["ncols"] == 1000 and got[1]["max_iter"] == 250
-    assert mine.out == theirs.out
+    assert mine.out == out
 
 
 def test_parser_known_values(host, tmp_path):
@@ -86,9 +99,8 @@ def test_environment_density_kat(host):
 
 def test_image_loader(host, tmp_path):
     want = maps.maze_6()
-    ref_png = "/root/reference/images/maze_6.png"
-    if os.path.exists(ref_png):
-        assert host_lib.load_image(host, ref_png).tobytes() == want.tobytes()
+    ref_png = os.path.join(GOLDEN, "maze_6.png")   # images/maze_6.png as the reference ships it
+    assert host_lib.load_image(host, ref_png).tobytes() == want.tobytes()
     # round trip through our own encoder: free <=> red channel == 255
     ny, nx = want.shape
     rgba = np.zeros((ny, nx, 4), np.uint8)
