@@ -213,7 +213,7 @@ int vhp_last_sweep_kernel(const vhp_ctx* ctx);
  * instead of its fields (option 2: one union field and one label field per device).  d_fields: n_fields fields of nx * ny
  * elements of `dtype` (the map's grid; "field_stride" elements apart as in vhp_sweep_batch_device); d_best: nx * ny elements of
  * dtype; d_arg: nx * ny int32.  n_fields = 0: best = -1, arg = INT32_MAX everywhere.  One pass over the fields, no temporaries;
- * asynchronous on the context's stream.
+ * asynchronous on the context's stream.  Not timed: vhp_last_elapsed_ms still reports the sweep or planner call before it.
  * vhp_union_partials_device: the same reduction over n_parts PARTIAL results -- d_bests: n_parts packed union fields, d_args: their
  * n_parts packed label fields (e.g. the partials of all devices after an all-gather); a tie goes to the lowest label. */
 int vhp_union_fields_device(vhp_ctx* ctx, const void* d_fields, int n_fields, int dtype, int first_index, void* d_best, int32_t* d_arg);

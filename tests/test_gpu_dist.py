@@ -98,3 +98,119 @@ def test_bench_two_ranks_on_one_device():
     assert d["config"]["self_check"]["equal"] is True
     wc = d["value_with_collective"]
     assert "error" not in wc and wc["allgather_f32"]["value"] > 0 and wc["union_fields"]["value"] > 0, wc
+
+
+class _single_rank_group:
+    """a world-size-1 RCCL process group on cuda:0 for the duration of a with-block"""
+
+    def __enter__(self):
+        import torch
+        import torch.distributed as dist
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(_free_port())
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+        return self
+
+    def __exit__(self, *exc):
+        import torch.distributed as dist
+        dist.destroy_process_group()
+        return False
+
+
+def _padded_sweep(ctx, occ, src, pad, tdt, vdt):
+    """the batch swept into a buffer whose fields are nx*ny + pad elements apart (field_stride); returns the [n, ny, nx] view"""
+    import torch
+    ny, nx = occ.shape
+    stride = nx * ny + pad
+    ctx.set_option("field_stride", stride)
+    buf = torch.full((len(src) * stride,), float("nan"), dtype=tdt, device="cuda")
+    d_src = torch.from_numpy(np.ascontiguousarray(src, np.int32)).cuda()
+    ctx.sweep_batch_device(d_src.data_ptr(), len(src), buf.data_ptr(), dtype=vdt)
+    ctx.sync()
+    return buf.as_strided((len(src), ny, nx), (stride, nx, 1))
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_union_fields_reads_the_fields_stride_not_the_last_sweeps(oracle, dtype):
+    # a sweep with a field_stride leaves it set on the context: dist.union_fields must read its tensor as laid out (packed, or
+    # padded as the sweep wrote it), restore the option and the context's stream, and equal numpy's union of the oracle's fields
+    import torch
+    import vhp_amd
+    from importlib import import_module
+    from test_union import _numpy_union
+    vd = import_module("visibility-heuristic-path-planner_amd.dist")
+    tdt, vdt, npdt = (torch.float64, vhp_amd.F64, np.float64) if dtype == "f64" else (torch.float32, vhp_amd.F32, np.float32)
+    occ = maps.random_rect_map(200, 163, 12, 3, 30, 3, 30, 3)
+    ny, nx = occ.shape
+    src = maps.free_sources(occ, 9, 4)
+    want = np.stack([oracle.sweep_full(occ, int(x), int(y)) for x, y in src]).astype(npdt)
+    wb, wa = _numpy_union(want, 5)
+    with _single_rank_group():
+        ctx = vhp_amd.Context(0)
+        ctx.set_map(occ)
+        side = torch.cuda.Stream()
+        ctx.set_stream(side.cuda_stream)
+        with torch.cuda.stream(side):
+            fields = _padded_sweep(ctx, occ, src, 37, tdt, vdt)
+        assert np.array_equal(fields.cpu().numpy(), want)
+        for what, f in (("packed", fields.contiguous()), ("padded", fields), ("one field", fields[2:3]), ("every other field", fields[::2])):
+            first = 5 + (2 if what == "one field" else 0)
+            best, arg = vd.union_fields(f, first, 5 + len(src), ctx=ctx)
+            torch.cuda.synchronize()
+            sub = want[[2]] if what == "one field" else want[::2] if what == "every other field" else want
+            eb, ea = _numpy_union(sub, first)
+            if what in ("packed", "padded"):
+                assert np.array_equal(eb, wb) and np.array_equal(ea, wa)
+            assert np.array_equal(best.cpu().numpy(), eb), "%s %s: union differs" % (dtype, what)
+            assert np.array_equal(arg.cpu().numpy(), ea.astype(np.int64)), "%s %s: arg-source differs" % (dtype, what)
+            assert ctx.stream == side.cuda_stream and ctx.field_stride == nx * ny + 37, what
+        # the context's own option still places the next sweep's fields where the caller asked
+        with torch.cuda.stream(side):
+            again = _padded_sweep(ctx, occ, src, 37, tdt, vdt)
+        assert np.array_equal(again.cpu().numpy(), want)
+
+
+def test_union_leaves_the_sweeps_elapsed_time():
+    # vhp_last_elapsed_ms reports the most recent sweep or planner call (include/vhp.h): a union behind the sweep does not replace it
+    import torch
+    import vhp_amd
+    from importlib import import_module
+    vd = import_module("visibility-heuristic-path-planner_amd.dist")
+    occ = maps.random_rect_map(328, 300, 30, 3, 40, 3, 40, 5)
+    src = maps.free_sources(occ, 8, 8)
+    with _single_rank_group():
+        ctx = vhp_amd.Context(0)
+        ctx.set_map(occ)
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        out = torch.empty((len(src),) + occ.shape, dtype=torch.float64, device="cuda")
+        d_src = torch.from_numpy(np.ascontiguousarray(src, np.int32)).cuda()
+        ctx.sweep_batch_device(d_src.data_ptr(), len(src), out.data_ptr())
+        ms = ctx.last_elapsed_ms()
+        assert ms > 0
+        best = torch.empty(occ.shape, dtype=torch.float64, device="cuda")
+        arg = torch.empty(occ.shape, dtype=torch.int32, device="cuda")
+        ctx.union_fields_device(out.data_ptr(), len(src), best.data_ptr(), arg.data_ptr())
+        assert ctx.last_elapsed_ms() == ms
+        vd.union_fields(out, 0, len(src), ctx=ctx)
+        torch.cuda.synchronize()
+        assert ctx.last_elapsed_ms() == ms
+
+
+def test_union_fields_refuses_fields_that_do_not_fit_the_context():
+    import torch
+    import vhp_amd
+    from importlib import import_module
+    vd = import_module("visibility-heuristic-path-planner_amd.dist")
+    with _single_rank_group():
+        ctx = vhp_amd.Context(0)
+        ctx.set_map(np.ones((30, 40), np.uint8))
+        ok = torch.zeros((3, 30, 40), dtype=torch.float64, device="cuda")
+        for bad in (torch.zeros((3, 40, 30), dtype=torch.float64, device="cuda"), torch.zeros((3, 30, 41), dtype=torch.float64, device="cuda"),
+                    torch.zeros((30, 40), dtype=torch.float64, device="cuda"), ok.half(), ok.to(torch.int32), ok.bfloat16()):
+            with pytest.raises(ValueError):
+                vd.union_fields(bad, 0, 3, ctx=ctx)
+        best, arg = vd.union_fields(ok, 0, 3, ctx=ctx)
+        torch.cuda.synchronize()
+        assert (best == 0).all() and (arg == 0).all()

@@ -93,3 +93,311 @@ def test_latency_sweep_register_budget(tmp_path):
             if fp64 >= 90:   # (~300 instructions: a window's sixteen steps)
                 n = len(re.findall(r"v_(?:readlane|writelane)_b32", blk))
                 assert n <= 2, "%s: %d spilled scalars moved inside a window's steps" % (name, n)
+
+
+# ---- wait states around the hand-written instructions -------------------------------------------------------------------------
+# The compiler's hazard recognizer pads what IT emits; it does not look inside an asm statement, neither at the instructions there
+# nor at the compiler's own instructions next to them.  The wait states such an instruction needs are the CDNA3/CDNA4 ISA's table of
+# manually inserted wait states (LLVM's GCNHazardRecognizer implements the same table for gfx940/gfx950, which is where the numbers
+# below are checked against):
+#   - a DPP read: no VALU write of a VGPR it reads within 2 wait states; no EXEC write within 5 (checkDPPHazards: DppVgprWaitStates,
+#     DppExecWaitStates);
+#   - a VMEM store of more than 64 bits of data (global_store_dwordx3/x4): its data VGPRs not written by a VALU instruction within the
+#     2 wait states that follow it (checkVALUHazards; gfx940+ needs 2 where gfx9 needed 1 -- the `s_nop 1` that ends the asm store).
+# A wait state is one per instruction and N+1 for `s_nop N`; comments, labels and directives are none.  Where the count reaches a
+# basic block's label, every predecessor is followed: the fall-through block and every branch to that label.
+DPP_VGPR_WS, DPP_EXEC_WS, WIDE_STORE_DATA_WS = 2, 5, 2
+# every mnemonic that may appear inside an asm statement, and the rule it is held to (None: it reads and writes no VGPR, or nothing
+# this table covers).  A hand-written instruction of any other kind fails the test until it is given a rule here.
+_ASM_RULES = {"s_nop": None, "s_waitcnt": None, "s_sleep": None, "v_mov_b32_dpp": "dpp", "global_store_dwordx4": "store", "global_store_dwordx3": "store"}
+_BRANCH = re.compile(r"^s_(?:c)?branch\w*$")
+_ENDS_BLOCK = {"s_branch", "s_endpgm", "s_setpc_b64", "s_trap"}
+
+
+class Unprovable(AssertionError):
+    pass
+
+
+class _Insn:
+    __slots__ = ("line", "op", "args", "in_asm")
+
+    def __init__(self, line, text, in_asm):
+        self.line = line
+        parts = text.split(None, 1)
+        self.op = parts[0]
+        self.args = [a.strip() for a in re.split(r",(?![^\[]*\])", parts[1])] if len(parts) > 1 else []
+        self.in_asm = in_asm
+
+    def wait_states(self):
+        return int(self.args[0], 0) + 1 if self.op == "s_nop" else 1
+
+    def __str__(self):
+        return "%s %s" % (self.op, ", ".join(self.args))
+
+
+def _vgprs(operand):
+    """the VGPR numbers an operand names: v7 -> {7}, v[52:53] -> {52, 53}"""
+    out = set()
+    for m in re.finditer(r"(?<![\w\[])v(\d+)\b|(?<![\w])v\[(\d+):(\d+)\]", operand):
+        if m.group(1) is not None:
+            out.add(int(m.group(1)))
+        else:
+            out.update(range(int(m.group(2)), int(m.group(3)) + 1))
+    return out
+
+
+def _valu_writes(insn):
+    """the VGPRs a VALU instruction writes (its first operand; both operands of a swap)"""
+    if not insn.op.startswith("v_") or not insn.args:
+        return set()
+    if insn.op.startswith(("v_readlane", "v_readfirstlane", "v_cmp_")):
+        return set()
+    n = 2 if insn.op.startswith(("v_swap", "v_permlane")) else 1
+    return set().union(*[_vgprs(a) for a in insn.args[:n]])
+
+
+def _writes_exec(insn):
+    if insn.op.startswith("v_cmpx") or "exec" in insn.op:
+        return True
+    return bool(insn.args) and insn.args[0] in ("exec", "exec_lo", "exec_hi") and (insn.op.startswith("s_") or insn.op.startswith("v_"))
+
+
+class _Function:
+    """One function of an assembly listing: its instructions and labels in program order, and the branches into every label."""
+
+    def __init__(self, name, body, is_kernel=True):
+        self.name, self.is_kernel = name, is_kernel
+        self.items = []       # ("insn", _Insn) | ("label", name)
+        self.branches = {}    # label -> [index of a branch instruction to it]
+        self.referenced = set()
+        in_asm = False
+        for no, raw in enumerate(body.splitlines()):
+            s = raw.strip()
+            if s.startswith(";;#ASMSTART"):
+                in_asm = True
+                continue
+            if s.startswith(";;#ASMEND"):
+                in_asm = False
+                continue
+            m = re.match(r"^(\.LBB\w+|\.Ltmp\w+):", s)
+            if m:
+                self.items.append(("label", m.group(1)))
+                continue
+            s = s.split(";", 1)[0].strip()
+            if not s or s.startswith("."):
+                continue
+            insn = _Insn(no, s, in_asm)
+            for lab in re.findall(r"\.LBB\w+", s):
+                if _BRANCH.match(insn.op):
+                    self.branches.setdefault(lab, []).append(len(self.items))
+                else:
+                    self.referenced.add(lab)
+            self.items.append(("insn", insn))
+
+    def hazard_before(self, i, need, bad, memo=None):
+        """Walk back from item i: the first instruction `bad` accepts within `need` wait states of it, or None."""
+        memo = {} if memo is None else memo
+        key = (i, need)
+        if key in memo:
+            return memo[key]
+        memo[key] = None   # (a loop back to here adds wait states: not a shorter path)
+        j = i - 1
+        res = None
+        while True:
+            if j < 0:
+                if not self.is_kernel:
+                    raise Unprovable("%s: reached the entry of a non-kernel function" % self.name)
+                break   # (the wave's first instruction: nothing before it)
+            kind, x = self.items[j]
+            if kind == "label":
+                if x in self.referenced:
+                    raise Unprovable("%s: %s is reached by a computed jump" % (self.name, x))
+                for b in self.branches.get(x, []):
+                    res = self.hazard_before(b + 1, need, bad, memo)
+                    if res:
+                        break
+                if res:
+                    break
+                if j > 0 and self.items[j - 1][0] == "insn" and self.items[j - 1][1].op in _ENDS_BLOCK:
+                    break   # (no fall-through into this label)
+                j -= 1
+                continue
+            if bad(x):
+                res = x
+                break
+            need -= x.wait_states()
+            if need <= 0:
+                break
+            j -= 1
+        memo[key] = res
+        return res
+
+    def hazard_after(self, i, need, bad, memo=None):
+        """Walk forward from item i: the first instruction `bad` accepts within `need` wait states after it, or None."""
+        memo = {} if memo is None else memo
+        key = (i, need)
+        if key in memo:
+            return memo[key]
+        memo[key] = None
+        j = i + 1
+        res = None
+        while j < len(self.items):
+            kind, x = self.items[j]
+            if kind == "label":
+                j += 1
+                continue
+            if bad(x):
+                res = x
+                break
+            need -= x.wait_states()
+            if need <= 0:
+                break
+            if _BRANCH.match(x.op):
+                tgt = [t for t in range(len(self.items)) if self.items[t] == ("label", x.args[0])]
+                if not tgt:
+                    raise Unprovable("%s: branch to %s outside the function" % (self.name, x.args[0]))
+                res = self.hazard_after(tgt[0], need, bad, memo)
+                if res or x.op == "s_branch":
+                    break
+            if x.op in ("s_endpgm", "s_setpc_b64"):
+                break
+            j += 1
+        memo[key] = res
+        return res
+
+    def check(self):
+        """[(rule, the hand-written instruction, the instruction too close to it)], and the count of hand-written DPP reads"""
+        found, n_dpp = [], 0
+        for i, (kind, x) in enumerate(self.items):
+            if kind != "insn" or not x.in_asm:
+                continue
+            if x.op not in _ASM_RULES:
+                found.append(("no rule for a hand-written %s" % x.op, x, None))
+                continue
+            rule = _ASM_RULES[x.op]
+            if rule == "dpp":
+                n_dpp += 1
+                reads = set().union(*[_vgprs(a) for a in x.args[:2]])   # (the source, and the destination: its old value is kept where no lane feeds it)
+                h = self.hazard_before(i, DPP_VGPR_WS, lambda y: bool(_valu_writes(y) & reads))
+                if h:
+                    found.append(("VALU write of a DPP source within %d wait states" % DPP_VGPR_WS, x, h))
+                h = self.hazard_before(i, DPP_EXEC_WS, _writes_exec)
+                if h:
+                    found.append(("EXEC write within %d wait states of a DPP read" % DPP_EXEC_WS, x, h))
+            elif rule == "store":
+                data = _vgprs(x.args[0] if x.op.startswith("buffer_") else x.args[1])
+                h = self.hazard_after(i, WIDE_STORE_DATA_WS, lambda y: bool(_valu_writes(y) & data))
+                if h:
+                    found.append(("VALU write of a wide store's data within %d wait states" % WIDE_STORE_DATA_WS, x, h))
+        return found, n_dpp
+
+
+def _functions(asm):
+    """every function of a listing: {name: _Function}"""
+    out = {}
+    kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M))
+    for name in re.findall(r"^\s*\.type\s+([\w.$]+),@function", asm, re.M):
+        m = re.search(r"^%s:[^\n]*\n(.*?)\n\.Lfunc_end\d+:" % re.escape(name), asm, re.S | re.M)
+        if m:
+            out[name] = _Function(name, m.group(1), name in kernels)
+    return out
+
+
+def _hazards(asm):
+    fns = _functions(asm)
+    report, dpp = [], {}
+    for name, fn in fns.items():
+        found, n = fn.check()
+        dpp[name] = n
+        report += ["%s: %s: `%s` (line %d of the body) <- `%s`" % (name, rule, x, x.line, h if h else "-") for rule, x, h in found]
+    return fns, report, dpp
+
+
+@pytest.mark.parametrize("src", ["vhp_lat.hip", "vhp_pool.hip", "vhp_capi.hip", "vhp_multi.hip"])
+def test_hand_written_instructions_have_their_wait_states(tmp_path, src):
+    asm = _asm(src, tmp_path)
+    try:
+        fns, report, dpp = _hazards(asm)
+    except Unprovable as e:
+        pytest.fail("unprovable: %s" % e)
+    assert not report, "%d hazard(s):\n%s" % (len(report), "\n".join(report[:20]))
+    if src == "vhp_lat.hip":
+        lat = {k: v for k, v in dpp.items() if "vhp_lat_sweep" in k}
+        print("inline DPP reads per latency-sweep instantiation:", lat)
+        assert len(lat) == 8, list(lat)
+        # (shift_up_into: one pair of DPP moves, low and high half, per use)
+        assert all(n >= 2 and n % 2 == 0 for n in lat.values()), lat
+        assert re.search(r"global_store_dwordx4 [^\n]* sc1", asm), "the agent-scope tagged store is gone from the latency sweep"
+    if src == "vhp_capi.hip":
+        assert len(fns) >= 30, sorted(fns)
+
+
+# the checker itself, on short listings (assembled by nobody, run nowhere)
+def _fn(body):
+    return _Function("f", "\n".join("\t" + l if not l.startswith((".LBB", ";;")) else l for l in body.strip().splitlines()))
+
+
+def _dpp_report(body):
+    return [r for r, _, _ in _fn(body).check()[0]]
+
+
+_DPP = ";;#ASMSTART\nv_mov_b32_dpp v6, v53 wave_shr:1 row_mask:0xf bank_mask:0xf\n;;#ASMEND"
+
+
+def test_checker_catches_a_valu_write_right_before_a_dpp():
+    assert _dpp_report("v_add_f64 v[52:53], v[52:53], 1.0\n" + _DPP)
+    assert _dpp_report("v_mov_b32_e32 v53, 0\nv_nop\n" + _DPP), "one wait state is not two"
+
+
+def test_checker_counts_s_nop_0_as_one_wait_state():
+    assert _dpp_report("v_mov_b32_e32 v53, s0\ns_nop 0\n" + _DPP)
+
+
+def test_checker_follows_predecessor_blocks():
+    # the write at the end of a block that branches to the DPP's block
+    body = """
+v_mov_b32_e32 v53, 0
+s_cbranch_scc1 .LBB0_2
+s_nop 7
+s_branch .LBB0_3
+.LBB0_2:
+""" + _DPP + """
+.LBB0_3:
+s_endpgm"""
+    rep = _dpp_report(body)
+    assert rep and "VALU write" in rep[0]
+    # ... and the fall-through predecessor
+    assert _dpp_report("s_nop 4\nv_mov_b32_e32 v53, 0\n.LBB0_1:\n" + _DPP)
+    # a block reached only by a branch from far enough away is fine: no fall-through into a label behind an s_endpgm
+    assert not _dpp_report("v_mov_b32_e32 v53, 0\ns_nop 1\ns_branch .LBB0_1\n.LBB0_5:\nv_mov_b32_e32 v53, 0\ns_endpgm\n.LBB0_1:\n" + _DPP)
+
+
+def test_checker_expands_register_ranges():
+    assert _dpp_report("v_fma_f64 v[52:53], v[0:1], v[2:3], v[4:5]\ns_nop 0\n" + _DPP)
+    assert _vgprs("v[52:53]") == {52, 53} and _vgprs("v5") == {5} and _vgprs("vcc") == set()
+
+
+def test_checker_catches_an_exec_write_before_a_dpp():
+    assert _dpp_report("s_and_saveexec_b64 s[4:5], vcc\ns_nop 2\n" + _DPP)
+    assert _dpp_report("s_or_b64 exec, exec, s[4:5]\n" + _DPP)
+    assert not _dpp_report("s_or_b64 exec, exec, s[4:5]\ns_nop 4\n" + _DPP)
+
+
+def test_checker_accepts_enough_wait_states():
+    assert not _dpp_report("v_mov_b32_e32 v53, 0\n;;#ASMSTART\ns_nop 1\n;;#ASMEND\n" + _DPP)
+    assert not _dpp_report("v_mov_b32_e32 v53, 0\nv_mov_b32_e32 v1, 0\nv_add_u32_e32 v2, v3, v4\n" + _DPP)
+    assert not _dpp_report("v_mov_b32_e32 v52, 0\n" + _DPP), "v52 is not a source"
+
+
+def test_checker_wide_store_data():
+    store = ";;#ASMSTART\nglobal_store_dwordx4 v[42:43], v[38:41], off sc1\n%s;;#ASMEND\n"
+    assert _dpp_report(store % "" + "v_mov_b32_e32 v40, 0")
+    assert _dpp_report(store % "s_nop 0\n" + "v_mov_b32_e32 v40, 0")
+    assert not _dpp_report(store % "s_nop 1\n" + "v_mov_b32_e32 v40, 0")
+    assert not _dpp_report(store % "" + "v_mov_b32_e32 v37, 0\nv_mov_b32_e32 v42, 0\ns_endpgm")
+
+
+def test_checker_fails_unprovable_and_unknown():
+    with pytest.raises(Unprovable):
+        _Function("g", "\t" + _DPP.replace("\n", "\n\t"), is_kernel=False).check()
+    assert _dpp_report(";;#ASMSTART\nv_readfirstlane_b32 s0, v1\n;;#ASMEND")

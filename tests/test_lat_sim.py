@@ -141,3 +141,15 @@ def test_lat_sim_two_workgroups_per_unit(oracle, nx, ny, density):
         dtype = np.float32 if (W == 3) else np.float64
         _check(oracle, occ, src, "%dx%d density %.2f W=%d policy=%d, %d workgroups per unit" % (nx, ny, density, W, policy, halves), dtype, W=W, policy=policy, seed=nx + W,
                halves=halves)
+
+
+@pytest.mark.parametrize("nx,ny", [(40, 33), (101, 101), (200, 163), (8, 200), (264, 9), (690, 402)])
+def test_lat_sim_blocked_repeated_sources_and_occupancy_bytes(oracle, nx, ny):
+    # the inputs tests/test_gpu_inputs.py gives the gfx950 build: sources on blocked cells, repeated sources, free cells that hold 2,
+    # 128 or 255 instead of 1 (the answer is the oracle's on occ != 0), and the whole-map cases
+    from edge_inputs import edge_map, whole_maps
+    occ, src = edge_map(nx, ny, nx * 5 + ny)
+    for byte, (W, policy, dtype) in zip((1, 2, 128, 255), SHAPES[:4]):
+        _check(oracle, (occ * np.uint8(byte)).astype(np.uint8), src, "%dx%d free byte %d W=%d" % (nx, ny, byte, W), dtype, W=W, policy=policy, seed=nx + byte)
+    for name, occ, src in whole_maps(nx, ny):
+        _check(oracle, occ, src, "%dx%d %s" % (nx, ny, name), W=12, policy=POOL_RANDOM | POOL_POINTS_RANDOM, seed=2)

@@ -183,3 +183,17 @@ def test_sims_under_address_sanitizer(tmp_path):
     env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0", VHP_SIM_LIB="libvhp_pool_sim_asan.so")
     r = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "asan-clean" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+@pytest.mark.parametrize("nx,ny", [(40, 33), (101, 101), (200, 163), (202, 163), (8, 200), (264, 9)])
+def test_pool_sim_blocked_repeated_sources_and_occupancy_bytes(oracle, nx, ny):
+    # the inputs tests/test_gpu_inputs.py gives the gfx950 build: sources on blocked cells, repeated sources, free cells that hold 2,
+    # 128 or 255 instead of 1 (the answer is the oracle's on occ != 0), and the whole-map cases
+    from edge_inputs import edge_map, whole_maps
+    occ, src = edge_map(nx, ny, nx * 3 + ny)
+    for byte, (W, C, G, policy, dtype) in zip((1, 2, 128, 255), SHAPES[:4]):
+        _check(oracle, (occ * np.uint8(byte)).astype(np.uint8), src, "%dx%d free byte %d W=%d G=%d" % (nx, ny, byte, W, G), dtype,
+               W=W, C=C, G=G, policy=policy, seed=nx + byte)
+    for name, occ, src in whole_maps(nx, ny):
+        for G in (1, 2):
+            _check(oracle, occ, src, "%dx%d %s G=%d" % (nx, ny, name, G), W=6, C=2, G=G, policy=POOL_RANDOM | POOL_POINTS_RANDOM, seed=G)

@@ -139,6 +139,8 @@ class Context:
             raise VhpError(rc, "vhp_create failed (no usable HIP device %d?)" % device)
         self.h = h
         self.nx = self.ny = 0
+        self.stream = 0           # the stream handle last given to set_stream (0: the default stream)
+        self.field_stride = 0     # the "field_stride" option as last set (vhp_set_map resets it to 0)
 
     def close(self):
         if getattr(self, "h", None):
@@ -154,15 +156,18 @@ class Context:
 
     def set_stream(self, stream_handle):
         self._check(self.lib.vhp_set_stream(self.h, C.c_void_p(stream_handle or 0)))
+        self.stream = stream_handle or 0
 
     def set_map(self, occ):
         occ = np.ascontiguousarray(occ, np.uint8)
         self.ny, self.nx = occ.shape
         self._check(self.lib.vhp_set_map(self.h, _ptr(occ), self.nx, self.ny))
+        self.field_stride = 0
 
     def set_map_device(self, dptr, nx, ny):
         self.nx, self.ny = nx, ny
         self._check(self.lib.vhp_set_map_device(self.h, C.c_void_p(dptr), nx, ny))
+        self.field_stride = 0
 
     def sweep_batch(self, sources, variant=SWEEP_FULL, dtype=F64):
         """Host-buffer form.  sources int32 [n, 2] (x, y) -> fields [n, ny, nx]."""
@@ -190,6 +195,8 @@ class Context:
     def set_option(self, key, value):
         """Launch-shape override (include/vhp.h vhp_set_option); 0 / -1 = automatic."""
         self._check(self.lib.vhp_set_option(self.h, key.encode(), int(value)))
+        if key == "field_stride":
+            self.field_stride = int(value)
 
     def last_sweep_kernel(self):
         """1 = front sweep, 3 = pool sweep, 4 = latency sweep: what the last batch sweep (or planner solve) launched."""

@@ -714,12 +714,10 @@ static int union_common(vhp_ctx* ctx, const char* who, const void* d_fields, int
   if (reinterpret_cast<uintptr_t>(d_fields) % el || reinterpret_cast<uintptr_t>(d_best) % el || reinterpret_cast<uintptr_t>(d_arg) % 4)
     return fail(ctx, VHP_ERR_ARG, std::string(who) + ": a pointer is not aligned to its element type");
   VHP_ON_DEVICE(ctx);
-  VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  // (not timed: ev0 / ev1 keep bracketing the most recent sweep or planner call, vhp_last_elapsed_ms)
   const hipError_t e = dtype == VHP_F64 ? vhp::launch_union<double>(d_fields, n, stride, d_labels, first_index, cells, d_best, d_arg, ctx->n_cus, ctx->stream)
                                         : vhp::launch_union<float>(d_fields, n, stride, d_labels, first_index, cells, d_best, d_arg, ctx->n_cus, ctx->stream);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
   return VHP_OK;
 }
 

@@ -291,10 +291,13 @@ VHP_LANE_FN vd shift_up(vd v, vd fill) {
 VHP_LANE_FN vd shift_up_into(vd& fill, vd v) {
   int flo = __double2loint(fill), fhi = __double2hiint(fill);
   const int lo = __double2loint(v), hi = __double2hiint(v);
-  // (s_nop 1: a DPP read needs two wait states after the vector instruction that wrote its source, and the compiler's hazard
-  // recognizer does not look inside an asm; the two sources were written by adjacent instructions, so one s_nop covers both)
-  asm("s_nop 1\n\tv_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(flo) : "v"(lo));
-  asm("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(fhi) : "v"(hi), "v"(flo));
+  // (s_nop 1: a DPP read needs two wait states after the vector instruction that wrote its source or old value, and the compiler's
+  // hazard recognizer does not look inside an asm.  Both moves are one statement with all four halves as operands, so every one of
+  // them is written before the statement begins and the s_nop that opens it covers both -- two statements would let the compiler
+  // put the producer of `hi` between them.  flo is early-clobber: the first move writes it before the second reads hi and fhi.
+  // tests/test_kernel_codegen.py checks the wait states in the gfx950 build.)
+  asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 wave_shr:1 row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %1, %3 wave_shr:1 row_mask:0xf bank_mask:0xf"
+               : "+&v"(flo), "+v"(fhi) : "v"(lo), "v"(hi));
   fill = __hiloint2double(fhi, flo);
   return fill;
 }

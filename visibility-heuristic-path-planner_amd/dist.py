@@ -92,27 +92,51 @@ def union_fields(local_fields, first_index, n_sources, ctx=None):
     shard in ONE pass over its fields (ctx given and the fields on its GPU: the HIP kernel behind vhp_union_fields_device --
     no temporaries; at BASELINE config 5 the torch expression this replaces made a 17 GB int64 temporary and read the 17 GB of
     fields four times), the partials -- one union field and one label field per rank -- are all-gathered (RCCL over xGMI, or
-    gloo), and every rank merges them (vhp_union_partials_device: a tie goes to the lowest label)."""
+    gloo), and every rank merges them (vhp_union_partials_device: a tie goes to the lowest label).  On the GPU path the fields must
+    be [n, ctx.ny, ctx.nx] float64 or float32 (ValueError otherwise); they are read at the tensor's own stride from one field to the
+    next, and the context's stream and "field_stride" option are as before on return."""
     world = dist.get_world_size()
     on_gpu = ctx is not None and local_fields.is_cuda
     shape = tuple(local_fields.shape[1:])
-    if on_gpu:
-        import vhp_amd
-        vdt = vhp_amd.F64 if local_fields.dtype == torch.float64 else vhp_amd.F32
-        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    if not on_gpu:
+        return _union_gathered(*_union_shim(local_fields, None, first_index), world, n_sources, None, None)
+    import vhp_amd
+    if local_fields.dim() != 3 or shape != (ctx.ny, ctx.nx):
+        raise ValueError("union_fields: fields of shape %r on a context whose grid is %r" % (tuple(local_fields.shape), (ctx.ny, ctx.nx)))
+    if local_fields.dtype not in (torch.float64, torch.float32):
+        raise ValueError("union_fields: fields of %s (float64 or float32 only)" % local_fields.dtype)
+    vdt = vhp_amd.F64 if local_fields.dtype == torch.float64 else vhp_amd.F32
+    # the kernel reads the fields "field_stride" elements apart: set to the tensor's own stride from one field to the next (every
+    # field itself packed) for this call -- never what the context's last sweep left there
+    cells = shape[0] * shape[1]
+    if local_fields.stride()[1:] != (shape[1], 1) or (local_fields.shape[0] > 1 and local_fields.stride(0) < cells):
         local_fields = local_fields.contiguous()
+    stride = local_fields.stride(0) if local_fields.shape[0] > 1 else cells
+    keep_stream, keep_stride = ctx.stream, ctx.field_stride
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    try:
         best = local_fields.new_empty(shape)
         arg = torch.empty(shape, dtype=torch.int32, device=local_fields.device)
-        ctx.union_fields_device(local_fields.data_ptr() if local_fields.shape[0] else best.data_ptr(), local_fields.shape[0], best.data_ptr(), arg.data_ptr(),
-                                first_index=first_index, dtype=vdt)
-    else:
-        best, arg = _union_shim(local_fields, None, first_index)
+        ctx.set_option("field_stride", stride)
+        try:
+            ctx.union_fields_device(local_fields.data_ptr() if local_fields.shape[0] else best.data_ptr(), local_fields.shape[0], best.data_ptr(), arg.data_ptr(),
+                                    first_index=first_index, dtype=vdt)
+        finally:
+            ctx.set_option("field_stride", keep_stride)
+        return _union_gathered(best, arg, world, n_sources, ctx, vdt)
+    finally:
+        ctx.set_stream(keep_stream)
+
+
+def _union_gathered(best, arg, world, n_sources, ctx, vdt):
+    """union_fields after the local reduction: all-gather the partials, merge them (on the GPU where ctx is given)."""
+    shape = tuple(best.shape)
     # concatenated-along-dim-0 form: accepted by both RCCL and gloo
     all_best = best.new_empty((world,) + shape)
     all_arg = arg.new_empty((world,) + shape)
     dist.all_gather_into_tensor(all_best.view((world * shape[0],) + shape[1:]), best.contiguous())
     dist.all_gather_into_tensor(all_arg.view((world * shape[0],) + shape[1:]), arg.contiguous())
-    if on_gpu:
+    if ctx is not None:
         gbest = best.new_empty(shape)
         garg = arg.new_empty(shape)
         ctx.union_partials_device(all_best.data_ptr(), all_arg.data_ptr(), world, gbest.data_ptr(), garg.data_ptr(), dtype=vdt)
