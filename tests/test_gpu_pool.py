@@ -157,7 +157,7 @@ def test_field_stride_pads_between_fields(vhp, oracle, kernel, nx, ny, pad):
 
 @pytest.mark.parametrize("nx,ny,n", [(1002, 700, 160), (1001, 971, 136), (690, 402, 192), (500, 500, 256)])
 def test_pool_is_the_default_for_batches_on_other_widths(vhp, oracle, nx, ny, n):
-    # the library's own choice (vhp_capi.hip use_pool_kernel) on widths that are not a multiple of 8: the pool sweep's ANYW build from
+    # the library's own choice (vhp_choice.hpp plan_sweep) on widths that are not a multiple of 8: the pool sweep's ANYW build from
     # these batch sizes up; every 8th field against the oracle, all of them written
     import torch
     occ = maps.random_rect_map(nx, ny, 40, 3, nx // 8, 3, ny // 8, nx + 5 * ny)

@@ -24,7 +24,7 @@ def _ctx(vhp, occ, **options):
     return c
 
 
-# the front sweep's shape for batches of 256+ sources (vhp_capi.hip pick_shape)
+# the front sweep's shape for batches of 256+ sources (vhp_choice.hpp plan_sweep)
 LINE_SHAPE = dict(rows_per_lane=1, strips=8, slide=1)
 
 
@@ -297,11 +297,11 @@ def test_config5_the_launch_that_ships(vhp, oracle):
     # with its queue contended and every kind of unit side by side; 16 of its fields (every 8th) against the oracle
     occ, src = maps.config_c5(128)
     kernel = _shipping_launch(vhp, oracle, occ, src, "C5 bench launch", 8)
-    assert kernel == 3  # the pool sweep (vhp_capi.hip use_pool_kernel): a threshold that moves must not silently change what this covers
+    assert kernel == 3  # the pool sweep (vhp_choice.hpp plan_sweep): a threshold that moves must not silently change what this covers
 
 
 def test_3072_sixtyfour_sources_the_launch_that_ships(vhp, oracle):
-    # the other threshold of the kernel choice (vhp_capi.hip use_pool_kernel): 64 sources from 3072 up
+    # the other threshold of the kernel choice (vhp_choice.hpp plan_sweep): 64 sources from 3072 up
     occ = maps.random_rect_map(3072, 3072, 50, 60, 300, 60, 300, seed=2)
     src = maps.free_sources(occ, 64, seed=13)
     assert _shipping_launch(vhp, oracle, occ, src, "3072^2 x 64", 8) == 3

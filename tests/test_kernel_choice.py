@@ -1,0 +1,138 @@
+"""The sweep's kernel choice (csrc/vhp_choice.hpp plan_sweep) over a grid of launches, against tests/golden/kernel_choice.json.
+
+CPU only: the header is host code, compiled here with the host C++ compiler into a small driver (tests/kernel_choice_driver.cpp).
+The grid takes every side at a rule's edge and one either side of it, widths that are a multiple of 8 and widths that are not,
+batch sizes at every threshold and one either side, both dtypes, three CU counts, each option that steers the choice, and each of
+lat_ok / pool_ok / lat_scratch_fits true and false.  The table pins what the library picks wherever no GPU test looks.
+
+Regenerate the table only when a crossover is meant to move:  python3 tests/test_kernel_choice.py --write
+(--include DIR builds the driver against the vhp_choice.hpp in DIR instead of the package's)."""
+import itertools
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "visibility-heuristic-path-planner_amd", "csrc")
+DRIVER = os.path.join(HERE, "kernel_choice_driver.cpp")
+TABLE = os.path.join(HERE, "golden", "kernel_choice.json")
+
+# sides where a rule changes its answer (vhp_choice.hpp: the front sweep's shape, the pool sweep's two ladders, the latency sweep's)
+EDGES = [64, 128, 256, 448, 450, 512, 576, 600, 640, 768, 896, 1024, 1100, 1280, 1792, 2560]
+SIDES = sorted({1, 8, 101, 4096, 8192} | {e + d for e in EDGES for d in (-1, 0, 1)})
+# batch sizes: every threshold and one either side, for 256 CUs (one round of octants = 32 sources), 80 (10) and 304 (38)
+SOURCES = sorted({1, 2, 4, 8, 1024, 4096} | {t + d for t in (10, 12, 16, 20, 24, 25, 28, 30, 32, 33, 38, 40, 47, 48, 64, 76, 80,
+                                                              95, 96, 114, 128, 256) for d in (-1, 0, 1)})
+SOURCES_FEW = [1, 8, 16, 17, 24, 27, 28, 32, 33, 40, 41, 47, 48, 64, 65, 80, 81, 96, 97, 128, 129, 255, 256, 257, 1024, 4096]
+SOURCES_OPT = [1, 8, 32, 33, 95, 96, 128, 255, 256, 257, 1024]
+AUTO = (0, 0, 0, 0, -1, 0)   # kernel rows_per_lane strips multi slide pack
+OPTIONS = ([(k, 0, 0, 0, -1, 0) for k in (1, 3, 4)] + [(0, r, 0, 0, -1, 0) for r in (1, 2, 4)] + [(0, 0, w, 0, -1, 0) for w in range(1, 9)]
+           + [(0, 0, 0, 1, -1, 0), (0, 0, 0, 0, 0, 0), (0, 0, 0, 0, 1, 0), (0, 0, 0, 0, -1, 1)])
+
+
+def shapes(side, every_width=True):
+    """(nx, ny) with the larger side `side`: square, wide, and with a width that is / is not a multiple of 8."""
+    out = {(side, side)}
+    if every_width:
+        out.add((side, max(1, side // 3)))
+        if side >= 8:
+            out.add((side - side % 8, side))
+    if side > 8:
+        out.add((side - side % 8 - 1, side))
+    return sorted(out)
+
+
+def grid():
+    """[(part, nx, ny, n_cus, f64, options, flags, sources)]: each group answered for every batch size in its list."""
+    g = []
+    for side in SIDES:
+        for nx, ny in shapes(side):
+            for n_cus, f64 in ((256, 1), (80, 1), (304, 1), (256, 0)):
+                g.append(("A", nx, ny, n_cus, f64, AUTO, (1, 1, 1), SOURCES))
+        for nx, ny in shapes(side, every_width=False):
+            for flags in itertools.product((0, 1), repeat=3):
+                if flags != (1, 1, 1):
+                    g.append(("B", nx, ny, 256, 1, AUTO, flags, SOURCES_FEW))
+    for side in (64, 65, 128, 129, 256, 257, 448, 449, 512, 513, 1024, 1025, 2560, 2561):
+        for nx, ny in shapes(side, every_width=False):
+            for f64, opts in itertools.product((1, 0), OPTIONS):
+                g.append(("C", nx, ny, 256, f64, opts, (1, 1, 1), SOURCES_OPT))
+    # every launch shape the front sweep can be asked for
+    for side, f64, r, w, m in itertools.product((64, 300, 1000, 3000), (1, 0), (0, 1, 2, 4), range(0, 9), (0, 1)):
+        g.append(("D", side, side, 256, f64, (0, r, w, m, -1, 0), (1, 1, 1), [1, 256]))
+    return g
+
+
+def key(row):
+    part, nx, ny, n_cus, f64, opts, flags, _ = row
+    return "%s %dx%d cus%d %s opt%s flags%s" % (part, nx, ny, n_cus, "f64" if f64 else "f32", ",".join(map(str, opts)),
+                                                "".join(map(str, flags)))
+
+
+def build_driver(out_dir, include=CSRC):
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler (set CXX)"
+    exe = os.path.join(out_dir, "kernel_choice_driver")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", include, "-o", exe, DRIVER])
+    return exe
+
+
+def dump(exe):
+    """{key: "KRWMS KRWMS*n ..."}: kernel, R, W, multi, slide per batch size of the group, runs of one plan as plan*length."""
+    g = grid()
+    lines = []
+    for part, nx, ny, n_cus, f64, opts, flags, sources in g:
+        for n in sources:
+            lines.append(" ".join(map(str, (nx, ny, n, n_cus, f64) + opts + flags)))
+    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split()
+    assert len(out) == len(lines)
+    table, i = {}, 0
+    for row in g:
+        runs = [(p, len(list(r))) for p, r in itertools.groupby(out[i:i + len(row[-1])])]
+        table[key(row)] = " ".join(p if n == 1 else "%s*%d" % (p, n) for p, n in runs)
+        i += len(row[-1])
+    return table
+
+
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    return dump(build_driver(str(tmp_path_factory.mktemp("kernel_choice"))))
+
+
+def test_kernel_choice_matches_table(table):
+    with open(TABLE) as f:
+        want = json.load(f)
+    assert want["sources"] == {"A": SOURCES, "B": SOURCES_FEW, "C": SOURCES_OPT, "D": [1, 256]}
+    assert sorted(table) == sorted(want["plans"]), "the grid and the table's keys differ"
+    diff = [(k, want["plans"][k], table[k]) for k in sorted(table) if table[k] != want["plans"][k]]
+    assert not diff, "plan_sweep moved away from the table at %d groups, e.g. %s" % (len(diff), diff[:3])
+
+
+def test_kernel_choice_table_is_not_vacuous(table):
+    plans = [p.split("*")[0] for v in table.values() for p in v.split()]
+    assert {p[0] for p in plans} == {"1", "3", "4"}
+    front = {(int(p[1]), int(p[2]), int(p[3])) for p in plans if p[0] == "1"}
+    # the front sweep's builds: R = 1, 2, 4 in one round or several; R = 2 in several rounds is built for W <= 4
+    reachable = {(r, w, m) for r in (1, 2, 4) for w in range(1, 9) for m in (0, 1) if not (r == 2 and m and w > 4)}
+    assert front == reachable
+    assert {p[4] for p in plans if p[0] == "1"} == {"0", "1"}
+
+
+if __name__ == "__main__":
+    import argparse
+    import tempfile
+    ap = argparse.ArgumentParser(description="write tests/golden/kernel_choice.json from plan_sweep")
+    ap.add_argument("--write", action="store_true", required=True)
+    ap.add_argument("--include", default=CSRC, help="directory of the vhp_choice.hpp to build against")
+    args = ap.parse_args()
+    with tempfile.TemporaryDirectory() as d:
+        t = dump(build_driver(d, args.include))
+    with open(TABLE, "w") as f:
+        json.dump({"sources": {"A": SOURCES, "B": SOURCES_FEW, "C": SOURCES_OPT, "D": [1, 256]}, "plans": t}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote %d groups to %s" % (len(t), TABLE), file=sys.stderr)

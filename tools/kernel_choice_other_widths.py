@@ -1,5 +1,5 @@
 """The three batch kernels on one launch each (latency / pool / front sweep, kernel time in us) and the library's own choice: for re-measuring the kernel-choice rule
-(csrc/vhp_capi.hip use_lat_kernel / use_pool_kernel).  Diagnostic only.  usage: kernel_choice_other_widths.py NXxNYxSOURCES ..."""
+(csrc/vhp_choice.hpp plan_sweep).  Diagnostic only.  usage: kernel_choice_other_widths.py NXxNYxSOURCES ..."""
 import os, sys
 ROOT='/root/repo'
 sys.path.insert(0, ROOT)

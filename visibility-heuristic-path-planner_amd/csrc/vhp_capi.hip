@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "vhp_batch_launch.h"
+#include "vhp_choice.hpp"
 #include "vhp_sweep.hip.h"
 #include "vhp_planner.hip.h"
 #include "vhp_queue.hip.h"
@@ -48,7 +49,7 @@ struct vhp_ctx {
   int wpr = 0, wpc = 0;
   int* d_err = nullptr;
 
-  // scratch for the host-buffer sweep entry point
+  // grow-only scratch (grow), capacities in bytes; first the host-buffer sweep entry points' (stage_batch)
   int32_t* d_src = nullptr;
   size_t d_src_cap = 0;
   void* d_out = nullptr;
@@ -56,8 +57,9 @@ struct vhp_ctx {
   double* d_bnd = nullptr;  // boundary rows of multi-round sweeps (sides above W*64*R)
   size_t d_bnd_cap = 0;
   int* d_order = nullptr;   // launch order of the (source, quadrant) units (+ one int4 descriptor per workgroup)
-  int* d_lat_order = nullptr;  // launch order of the latency sweep's units where it launches more of them than the device has CUs
   size_t d_order_cap = 0;
+  int* d_lat_order = nullptr;  // launch order of the latency sweep's units where it launches more of them than the device has CUs
+  size_t d_lat_order_cap = 0;
   int* d_pool = nullptr;    // pool sweep: pull counter, unit order, diagonal lines, tagged boundary lines (zeroed when allocated)
   size_t d_pool_cap = 0;
   unsigned long long pool_epoch = 0x5A17000000000000ull;  // tag of the last pool launch
@@ -156,29 +158,6 @@ vhp::DevMap dev_map(const vhp_ctx* c) {
   return m;
 }
 
-// A workgroup sweeps one quadrant with 2*W wavefronts (W strips per octant) and R rows/columns
-// per lane.  Fronts longer than W*64*R are swept in rounds (`multi`).  Overridable for tuning
-// with VHP_R / VHP_W / VHP_MULTI.
-void pick_shape(const vhp_ctx* c, int maxdim, int* R, int* W, bool* multi, int n_src = 1, bool f64 = true, bool pitch64 = false) {
-  if (maxdim <= 64) { *R = 1; *W = 1; }
-  else if (maxdim <= 128) { *R = 2; *W = 1; }   // (one strip of two rows per lane per octant, no hand-over: 101^2 x 4096 sources 0.203 -> 0.191 ms, tools/small_grid_shapes.py)
-  else if (maxdim <= 256) { *R = 1; *W = 4; }
-  else if (maxdim <= 512) { *R = 2; *W = 4; }
-  else if (maxdim <= 1024) { *R = 2; *W = 8; }
-  else { *R = 4; *W = 8; }
-  // (Round 1 sent batches of 256+ sources to the one-row-per-lane shape with whole-line flushes: -3 % at 1000^2 then,
-  // +2 % when re-measured in round 2 (0.780 against 0.767 ms on one buffer); above 1024 such batches take the streaming
-  // sweep now.  The shape stays reachable through vhp_set_option and is parity-tested.)
-  // fp32 fields still do: there the 16 staged columns of that shape are one whole 64-byte sector per row, and the
-  // two-rows-per-lane shape spills 52 registers in its fp32 build (0.53 against 0.61 ms at 1000^2, round 1).
-  if (!f64 && maxdim > 256 && maxdim <= 1024 && n_src >= 256 && pitch64) { *R = 1; *W = 8; }
-  if (c && c->opt_rows_per_lane) *R = c->opt_rows_per_lane;
-  if (c && c->opt_strips) *W = c->opt_strips;
-  *multi = (*W) * 64 * (*R) < maxdim;
-  if (c && c->opt_multi) *multi = true;
-  if (*R == 2 && *multi && *W > 4) *W = 4;  // that build is compiled for 8-wavefront workgroups
-}
-
 }  // namespace
 
 namespace {
@@ -198,8 +177,61 @@ void free_map(vhp_ctx* c) {
   c->nx = c->ny = 0;
 }
 
+// Grow-only device scratch: reallocated (contents not kept) when `bytes` exceeds its capacity, zeroed when new if `zero`.
+template <typename T>
+hipError_t grow(T** p, size_t* cap_bytes, size_t bytes, bool zero, hipStream_t stream) {
+  if (*cap_bytes >= bytes) return hipSuccess;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap_bytes = 0;
+  hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess && zero) e = hipMemsetAsync(*p, 0, bytes, stream);
+  if (e == hipSuccess) *cap_bytes = bytes;
+  return e;
+}
+
+// A launch's timing events while vhp_timing is on (else none): a recycled pair, or a new one.
+using EventPair = std::pair<hipEvent_t, hipEvent_t>;
+hipError_t acquire_events(vhp_ctx* c, EventPair* ev) {
+  *ev = {nullptr, nullptr};
+  if (!c->timing) return hipSuccess;
+  if (!c->event_pool.empty()) { *ev = c->event_pool.back(); c->event_pool.pop_back(); return hipSuccess; }
+  if (hipEventCreate(&ev->first) != hipSuccess) return hipErrorOutOfMemory;
+  if (hipEventCreate(&ev->second) == hipSuccess) return hipSuccess;
+  (void)hipEventDestroy(ev->first);
+  return hipErrorOutOfMemory;
+}
+// ... timed if the launch went out; back to the pool if it failed (a pair that was never recorded can never be waited for)
+void release_events(vhp_ctx* c, const EventPair& ev, hipError_t launched) {
+  if (ev.first) (launched == hipSuccess ? c->timed_launches : c->event_pool).push_back(ev);
+}
+
+// What sweeps a batch of n_src sources on the context's grid with its options (vhp_choice.hpp).
+vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) {
+  const bool lat_ok = vhp::lat_supported(c->nx, c->ny);
+  return vhp::plan_sweep({c->nx, c->ny, n_src, c->n_cus, f64,
+                          {c->opt_kernel, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, lat_ok,
+                          vhp::pool_supported(c->nx, c->ny), lat_ok && vhp::lat_scratch_bytes(n_src, c->nx, c->ny) <= ((size_t)2 << 30)});
+}
+
+// The planner's sweeps of n_src sources: the plan, and the front sweep's shape and round scratch (n_workgroups) from it.
+hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workgroups, vhp::SweepPlan* plan) {
+  *plan = plan_for(ctx, n_src, true);
+  hipError_t e = vhp::attach_round_scratch(pm, plan->W * 64 * plan->R, n_workgroups, &ctx->d_bnd, &ctx->d_bnd_cap);
+  if (e != hipSuccess) return e;
+  ctx->pl.R = plan->R;
+  ctx->pl.W = plan->W;
+  ctx->pl.multi = plan->multi;
+  ctx->pl.raise_lds = [ctx](const void* fn, size_t bytes) { return raise_lds_limit(ctx, fn, bytes); };
+  ctx->last_kernel = plan->kernel == 4 ? 4 : 1;  // (vhp_last_sweep_kernel after a solve: what swept its iterations)
+  return hipSuccess;
+}
+
+// The front sweep: a workgroup sweeps one quadrant with 2*W wavefronts (W strips per octant) and R rows/columns per lane;
+// fronts longer than W*64*R are swept in rounds (MULTI).
 template <int R, bool MULTI, typename OutT>
-hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, int W) {
+hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& plan) {
+  const int W = plan.W;
   const bool pack = c->opt_pack != 0;
   const size_t lds = vhp::sweep_lds_bytes(R, W, MULTI, pack);
   auto k = vhp::vhp_sweep_fronts<R, MULTI, OutT>;
@@ -209,39 +241,19 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
   }
   const long long stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)c->nx * c->ny;
   vhp::DevMap m = dev_map(c);
-  // Sliding the y-major column grid onto 128-byte lines pays in the store-bound regime (many quadrants in flight:
-  // +1 % at 1000^2, +3.5 % at 4096^2); a lone quadrant is latency-bound, and there the predicated stores of the
-  // slid strip 0 -- the busiest wavefront -- cost 9 %.
-  m.slide = n_src >= 96 ? 1 : 0;
-  if (c->opt_slide >= 0) m.slide = c->opt_slide;
+  m.slide = plan.slide;
   hipError_t eb = vhp::attach_round_scratch(m, W * 64 * R, (size_t)n_src * vhp::kUnitsPerSource, &c->d_bnd, &c->d_bnd_cap);
   if (eb != hipSuccess) return eb;
   const size_t n_units = (size_t)n_src * vhp::kUnitsPerSource;
   const int* order = nullptr;
   const int4* desc = nullptr;
   // per-launch timing: from before the unit-ordering pre-kernel (part of what a launch costs) to after the sweep
-  hipEvent_t ta = nullptr, tb = nullptr;
-  if (c->timing) {
-    if (!c->event_pool.empty()) {
-      ta = c->event_pool.back().first;
-      tb = c->event_pool.back().second;
-      c->event_pool.pop_back();
-    } else {
-      if (hipEventCreate(&ta) != hipSuccess) return hipErrorOutOfMemory;
-      if (hipEventCreate(&tb) != hipSuccess) { (void)hipEventDestroy(ta); return hipErrorOutOfMemory; }
-    }
-  }
-  auto give_back = [&]() { if (ta) c->event_pool.push_back({ta, tb}); };
-  if (ta) (void)hipEventRecord(ta, c->stream);
+  EventPair ev;
+  if (hipError_t ee = acquire_events(c, &ev); ee != hipSuccess) return ee;
+  if (ev.first) (void)hipEventRecord(ev.first, c->stream);
   if (n_src >= 8) {  // worth a 1-workgroup pre-kernel once the batch spans many CUs
-    if (c->d_order_cap < n_units) {
-      if (c->d_order) (void)hipFree(c->d_order);
-      c->d_order = nullptr;
-      c->d_order_cap = 0;
-      hipError_t eo = hipMalloc(&c->d_order, n_units * (sizeof(int) + sizeof(int4)) + 16);
-      if (eo != hipSuccess) { give_back(); return eo; }
-      c->d_order_cap = n_units;
-    }
+    hipError_t eo = grow(&c->d_order, &c->d_order_cap, n_units * (sizeof(int) + sizeof(int4)) + 16, false, c->stream);
+    if (eo != hipSuccess) { release_events(c, ev, eo); return eo; }
     int4* d_desc = reinterpret_cast<int4*>(c->d_order);                      // n_units descriptors first (16-byte aligned)
     int* d_ord = reinterpret_cast<int*>(d_desc + n_units);                   // then the order list
     // Packing short quadrants into one workgroup is implemented and parity-tested, but measured slower
@@ -255,132 +267,17 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
   const unsigned grid = (unsigned)n_units;
   hipLaunchKernelGGL(k, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, d_out, stride, c->d_err, order, desc);
   const hipError_t el = hipGetLastError();
-  if (ta) {
-    (void)hipEventRecord(tb, c->stream);
-    c->timed_launches.push_back({ta, tb});
-  }
+  if (ev.first) (void)hipEventRecord(ev.second, c->stream);
+  release_events(c, ev, el);
   return el;
 }
 
-// Which kernel sweeps a batch: the pool sweep (vhp_pool.hpp) is built for throughput -- a pool of wavefronts per CU pulling
-// strips of many units at once, whole-line non-temporal stores -- the front sweep (vhp_sweep.hip.h) takes what the two others
-// do not (33-191 sources, widths that are not a multiple of 8).
-// The latency sweep (vhp_lat.hpp): one workgroup per octant.  Measured on MI355X against the front sweep (tools/lat_vs_front.py,
-// kernel time in us, front / latency sweep): one source at 256^2 33 / 28, 512^2 70 / 55, 690^2 94 / 67, 1000^2 132 / 96, 1536^2
-// 291 / 176, 2048^2 380 / 244; 8 sources 65 / 47, 123 / 88, 176 / 130, 244 / 177, 607 / 362, 844 / 559; 32 sources 67 / 48, 138 / 92,
-// 178 / 131, 296 / 196, 644 / 377, 866 / 604; 64 sources (two workgroups per CU wanted, one fits) 68 / 85, 139 / 153, 187 / 213,
-// 300 / 317, 664 / 559, 999 / 1015; 3072^2: 1 / 8 / 32 sources 649 / 413, 1661 / 1171, 1771 / 1351; 4096^2: 8 / 32 sources 2543 / 1800,
-// 2886 / 2554.  So: every launch whose octants have a CU each.
-bool use_lat_kernel(const vhp_ctx* c, int n_src) {
-  if (c->opt_kernel != 0 && c->opt_kernel != 4) return false;
-  if (!vhp::lat_supported(c->nx, c->ny)) return false;
-  if (c->opt_kernel == 4) return n_src <= 256 && vhp::lat_scratch_bytes(n_src, c->nx, c->ny) <= ((size_t)2 << 30);
-  // (a caller that sets a launch shape of the front sweep is asking for the front sweep)
-  if (c->opt_rows_per_lane || c->opt_strips || c->opt_multi || c->opt_slide >= 0 || c->opt_pack) return false;
-  // Round 6, late: a long octant's bands go to two, four or eight workgroups (vhp_lat.hip lat_halves) -- while 16 x sources <= CUs.  With
-  // 17-32 sources on a large grid the octants are back to one workgroup each, rounds of eight bands, and the pool sweep is ahead
-  // (latency / pool sweep, us, profiles/r06_exp_workgroups_per_unit.txt): 2048^2: 16 sources 349 / 478, 24: 440 / 497, 32: 535 / 489;
-  // 3072^2: 16: 664 / 904, 24: 1094 / 927, 32: 1377 / 1010; 4096^2: 16: 1226 / 1575, 24: 2053 / 1646, 32: 2414 / 1660; 1536^2: 24: 227 / 332,
-  // 32: 280 / 332.  (Widths that are a multiple of 8: the pool sweep's other build was not measured against it.)
-  const int maxdim = std::max(c->nx, c->ny);
-  if ((c->nx & 7) == 0 && c->opt_kernel == 0 && vhp::pool_supported(c->nx, c->ny)) {
-    if (n_src > 16 && maxdim > 2560) return false;
-    if (n_src >= 28 && maxdim > 1792) return false;
-  }
-  // Round 6, last: MORE sources than octants fit the chip at once, up to 1024 cells a side.  The launch is as long as its longest octant
-  // while most octants are short, so the workgroups beyond the first 256 find CUs long before the long ones are through (latency /
-  // pool / front sweep, us, profiles/r06_exp_lat_beyond_one_octant_per_cu.txt): 320^2: 48 sources 51 / 92 / 87, 64: 62 / 96 / 87;
-  // 512^2: 48: 84 / 131 / 128, 64: 107 / 134 / 128; 640^2: 64: 132 / 159 / 165; 768^2: 48: 157 / 192 / 221, 64: 190 / 193 / 220; 896^2: 48: 166 /
-  // 207 / 250, 64: 214 / 210 / 252; 1000^2: 36: 155 / 234, 44: 201 / 234, 52: 220 / 234, 56: 269 / 237, 64: 273 / 242; from 96 sources the others
-  // are ahead everywhere (512^2: 96: 128 / 127 / 138, 128: 156 / 132 / 145).  Other widths (the pool sweep's slower build): 64 sources at
-  // 1001 x 971 273 against the front sweep's 295 and the pool sweep's ~ 340; at 101^2 28 / 34, at 255^2 60 / 71 (front).
-  // ... and with the units launched by falling length of their march (vhp_lat.hip vhp_lat_order: the long octants start first, the short
-  // ones fill the CUs they leave; unordered / ordered / pool sweep): 1000^2: 40 sources 171 / 157 / 233, 48: 212 / 171 / 234, 64: 273 / 216 / 239,
-  // 96: 361 / 311 / 237; 768^2: 64: 190 / 125 / 197, 96: 234 / 187 / 181; 512^2: 64: 107 / 72 / 131, 96: 139 / 99 / 126, 128: 145 / 126 / 132.
-  // 896^2: 80: 177 / 213 (ordered / pool); 640^2: 96: 133 / 154, 128: 177 / 157; 256^2: 96: 54 / 71, 128: 67 / 71 (front); 128^2: 96: 36 / 46, 128: 44 / 46
-  // (front); 1280^2: 40: 229 / 291, 64: 342 / 287; 1536^2: 40: 365 / 335.
-  // So, in rounds of octants (32 sources on 256 CUs): four up to 256 cells a side, three up to 640, two and a half up to 896, two up to
-  // 1024, one and a quarter up to 1280, one above.
-  const int one_round = c->n_cus / 8;   // sources whose octants have a CU each
-  int cap = maxdim <= 256 ? 4 * one_round : maxdim <= 640 ? 3 * one_round : maxdim <= 896 ? one_round * 5 / 2 : maxdim <= 1024 ? 2 * one_round
-          : maxdim <= 1280 ? one_round * 5 / 4 : one_round;
-  // Widths that are not a multiple of 8, where the other two kernels store 8-byte cells or run their slower build (tools/kernel_choice_other_widths.py,
-  // latency / pool / front, us): 1001 x 971: 64 sources 234 / 360 / 287, 128: 335 / 375 / 433; 1002 x 1000: 96: 281 / 327 / 378; 689^2: 80: 137 / 254 /
-  // 191, 128: 230 / 262 / 278; 690 x 402: 128: 160 / 182 / 171; 500^2: 128: 146 / 170 / 147; 1101 x 1100: 64: 274 / 380 / 392; 1201 x 1200: 40: 241 / 416 /
-  // 435; but 255^2: 128: 78 / 112 / 72, 101^2: 128: 44 / 57 / 39.  Four rounds up to 1280 cells a side, three up to 256.
-  if ((c->nx & 7) != 0) cap = maxdim <= 256 ? 3 * one_round : maxdim <= 1280 ? 4 * one_round : one_round;
-  // (the boundary lines of a launch -- 16 bytes per strip and step -- stay below two gigabytes: 32 sources at 8192^2 would take four)
-  return n_src <= std::min(cap, 128) && vhp::lat_scratch_bytes(n_src, c->nx, c->ny) <= ((size_t)2 << 30);
-}
-
-bool use_pool_kernel(const vhp_ctx* c, int n_src) {
-  if (c->opt_kernel == 1 || c->opt_kernel == 4) return false;
-  if (!vhp::pool_supported(c->nx, c->ny)) return false;
-  if (c->opt_kernel == 3) return true;
-  // Measured on MI355X in round 3 (tools/ab_libs.py: three kernels on one buffer in one process; pool / streaming (since retired) / front, ms):
-  // 256 sources at 1000^2 0.51-0.55 / 0.61 / 0.56 on one box and 0.67-0.70 / 0.73 / 0.74 on another; 512: 0.96 / - / 1.03;
-  // 128: 0.44-0.46 / - / 0.45; 128 sources at 2048^2 1.25 / 1.42 / -; at 4096^2 3.88 / 4.29 / -.  The pool sweep from 192
-  // sources up to side 1024, and wherever the streaming sweep used to be picked above it.
-  // Round 4, with non-temporal stores and strips claimed ahead (tools/ab_libs.py, one buffer; front / pool, ms): 1000^2: 48 sources
-  // 0.293 / 0.289, 64: 0.298 / 0.295, 96: 0.353 / 0.321, 128: 0.424 / 0.399, 192: 0.593 / 0.511; 512^2: 96: 0.137 / 0.165, 192: 0.199 /
-  // 0.191, 384: 0.341 / 0.328; 2048^2: 32: 0.82 / 0.64, 48: 0.92 / 0.66, 64: 1.15 / 0.77, 96: 1.57 / 1.03; 4096^2: 24: 2.67 / 1.95, 48:
-  // 3.43 / 2.18, 64: 4.42 / 2.42.  (Up to 32 sources the latency sweep has taken the launch before this is asked.)
-  const int maxdim = std::max(c->nx, c->ny);
-  if ((c->nx & 7) != 0) {
-    // Widths that are not a multiple of 8 (the pool sweep's ANYW build; the front sweep stores
-    // 8-byte cells there).  Front / pool, us: 1002x1000: 48 sources 373 / 336, 96: 621 / 384, 192: 1107 / 670; 1001x971: 48: 367 / 361,
-    // 96: 639 / 394; 690x402: 48: 152 / 172, 96: 236 / 187, 192: 395 / 204; 500^2: 96: 166 / 196, 192: 280 / 209, 512: 663 / 462;
-    // 250^2: 192: 94 / 123, 512: 220 / 259; 101^2: 512: 50 / 191.
-    // (with the whole-line build: 1002x1000: 32: 309 / 329, 48: 365 / 320, 96: 621 / 394, 192: 1116 / 604; 690x402: 48: 152 / 189, 96: 240 / 195;
-    // 500^2: 96: 167 / 185, 192: 285 / 208; 398^2: 96: 132 / 150, 192: 213 / 174)
-    // Round 5, the front sweep with plain stores (1.5-1.9 x faster on these widths: vhp_sweep.hip.h StoreEmit; front / pool, us,
-    // profiles/r05_front_vs_pool_plain_front_stores.txt): 1002x1000: 48 sources 298 / 321, 96: 438 / 322, 256: 1013 / 626; 1001x971: 48: 281 /
-    // 337, 96: 425 / 353; 690x402: 96: 170 / 176, 192: 235 / 208, 256: 325 / 244; 500^2: 192: 171 / 182, 256: 265 / 238, 512: 521 / 438;
-    // 398^2: 256: 139 / 199, 512: 356 / 353; 250^2: 512: 108 / 248.
-    if (maxdim < 450) return false;
-    if (maxdim <= 600) return n_src >= 256;
-    if (maxdim <= 768) return n_src >= 128;
-    if (maxdim <= 1100) return n_src >= 64;
-    return n_src >= 24;
-  }
-  // (later in round 4, tools/kernel_ab.py, front / pool, us: 256^2: 192 sources 72 / 113, 384: 91 / 191; 384^2: 192: 124 / 148, 384: 175 / 249;
-  // 512^2: 192: 157 / 184, 384: 284 / 315; 640^2: 96: 186 / 211, 192: 296 / 247, 384: 477 / 403; 768^2: 96: 227 / 237, 192: 397 / 329)
-  // Round 5, with the strips in windows of 16 steps (profiles/r05_front_vs_pool_multiples_of_8.txt; front / pool, us): 320^2: 96 sources
-  // 99 / 92, 192: 101 / 108, 1024: 314 / 475; 384^2: 96: 116 / 107, 384: 226 / 209, 1024: 495 / 529; 448^2: 96: 132 / 122, 192: 168 / 142,
-  // 384: 286 / 244, 1024: 521 / 583; 512^2: 48: 135 / 137, 96: 144 / 131, 192: 201 / 168, 1024: 859 / 694; 576^2: 48: 150 / 146, 96: 164 / 142,
-  // 384: 446 / 332; 640^2: 48: 169 / 163, 384: 519 / 384; 768^2: 48: 220 / 193, 96: 248 / 207; 1000^2: 48: 296 / 233, 96: 328 / 257, 384: 1104 / 809.
-  // 256^2 and below: the front sweep at every batch size (256^2 x 4096: 911 / 1734; 104^2 x 4096: 247 / 1483).
-  // Again with the front sweep's plain stores (same file as above): 384^2: 96 sources 115 / 102, 192: 126 / 121, 384: 189 / 202; 448^2: 48:
-  // 118 / 124, 96: 133 / 118, 384: 274 / 242, 1024: 655 / 587; 512^2: 48: 136 / 135, 96: 145 / 128, 1024: 823 / 691; 576^2: 48: 152 / 147;
-  // 640^2: 48: 172 / 162; 768^2: 48: 216 / 198; 1000^2: 48: 300 / 233.
-  if (maxdim < 448) return false;
-  if (maxdim < 576) return n_src >= 96;
-  if (maxdim < 768) return n_src >= 48;
-  if (maxdim <= 1024) return n_src >= 33;
-  if (maxdim > 2560) return n_src >= 17;   // (where the latency sweep has left the launch to this: use_lat_kernel)
-  return n_src >= 24;
-}
-
-// the pool sweep's scratch: its own allocation (nothing else may write the tagged lines), zero when new
-hipError_t ensure_pool_scratch(vhp_ctx* c, size_t bytes) {
-  if (c->d_pool_cap >= bytes) return hipSuccess;
-  if (c->d_pool) (void)hipFree(c->d_pool);
-  c->d_pool = nullptr;
-  c->d_pool_cap = 0;
-  hipError_t e = hipMalloc(&c->d_pool, bytes);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(c->d_pool, 0, bytes, c->stream);
-  if (e != hipSuccess) return e;
-  c->d_pool_cap = bytes;
-  return hipSuccess;
-}
-
+// The pool sweep (lat = false) or the latency sweep (lat = true), through vhp_batch_launch.h.
 template <typename OutT>
 hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, bool lat) {
-  {
-    hipError_t eo = ensure_pool_scratch(c, lat ? vhp::lat_scratch_bytes(n_src, c->nx, c->ny) : vhp::pool_scratch_bytes(n_src, c->nx, c->ny));
-    if (eo != hipSuccess) return eo;
-  }
+  // (the scratch is an allocation of its own: nothing but these two kernels may write the tagged lines)
+  const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, c->nx, c->ny) : vhp::pool_scratch_bytes(n_src, c->nx, c->ny);
+  if (hipError_t eo = grow(&c->d_pool, &c->d_pool_cap, scratch, true, c->stream); eo != hipSuccess) return eo;
   vhp::BatchArgs a;
   a.rows = c->d_rows; a.cols = c->d_cols; a.recip = c->d_recip; a.dmap = c->d_dmap;
   a.wpr = c->wpr; a.wpc = c->wpc; a.nx = c->nx; a.ny = c->ny;
@@ -397,15 +294,12 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT*
   a.d_run_if = lat ? c->lat_run_if : nullptr;
   a.lat_dead_cells_are_zero = lat && c->lat_dark_unwritten;
   a.lat_workgroups = c->opt_lat_workgroups;
-  if (lat && !c->d_lat_order) {
-    hipError_t eo = hipMalloc(&c->d_lat_order, vhp::lat_order_bytes());
-    if (eo != hipSuccess) return eo;
-  }
+  if (lat)
+    if (hipError_t eo = grow(&c->d_lat_order, &c->d_lat_order_cap, vhp::lat_order_bytes(), false, c->stream); eo != hipSuccess) return eo;
   a.d_lat_order = c->d_lat_order;
   a.n_cus = c->n_cus;
   a.stream = c->stream;
   a.raise_lds = [c](const void* fn, size_t bytes) { return raise_lds_limit(c, fn, bytes); };
-  a.ev_begin = a.ev_end = nullptr;
   a.pool_contexts = c->opt_pool_contexts;
   a.pool_claim_ahead = c->opt_pool_claim_ahead;
   a.pool_busy_cap = c->opt_pool_busy_cap;
@@ -414,56 +308,54 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT*
   a.pool_tail_pct = c->opt_pool_tail_pct;
   a.pool_heads = c->opt_pool_heads;
   a.pool_static_round = c->opt_pool_static_round;
-  if (c->timing) {
-    if (!c->event_pool.empty()) {
-      a.ev_begin = c->event_pool.back().first;
-      a.ev_end = c->event_pool.back().second;
-      c->event_pool.pop_back();
-    } else {
-      if (hipEventCreate(&a.ev_begin) != hipSuccess) return hipErrorOutOfMemory;
-      if (hipEventCreate(&a.ev_end) != hipSuccess) { (void)hipEventDestroy(a.ev_begin); return hipErrorOutOfMemory; }
-    }
-  }
+  EventPair ev;
+  if (hipError_t ee = acquire_events(c, &ev); ee != hipSuccess) return ee;
+  a.ev_begin = ev.first;
+  a.ev_end = ev.second;
   const hipError_t e = lat ? (c->planner_dev ? vhp::launch_lat_planner(a, *c->planner_dev) : vhp::launch_lat(a)) : vhp::launch_pool(a);
-  if (c->timing) {
-    // (a launch that failed before its events were recorded must not leave a pair that can never be waited for)
-    if (e == hipSuccess) c->timed_launches.push_back({a.ev_begin, a.ev_end});
-    else c->event_pool.push_back({a.ev_begin, a.ev_end});
-  }
+  release_events(c, ev, e);
   return e;
 }
 
 template <typename OutT>
 hipError_t launch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out) {
-  if (use_lat_kernel(c, n_src)) {
-    c->last_kernel = 4;
-    return launch_batch_sweep<OutT>(c, d_src, n_src, d_out, true);
-  }
-  if (use_pool_kernel(c, n_src)) {
-    c->last_kernel = 3;
-    return launch_batch_sweep<OutT>(c, d_src, n_src, d_out, false);
-  }
-  c->last_kernel = 1;
-  int R, W;
-  bool multi;
-  pick_shape(c, std::max(c->nx, c->ny), &R, &W, &multi, n_src, sizeof(OutT) == 8, (c->nx & 7) == 0);
-  if constexpr (sizeof(OutT) == 4) {
-    // fp32 fields: only the one-row-per-lane shape of the front sweep is built.  The two- and four-rows-per-lane fp32
-    // instantiations needed 72-276 bytes of scratch per lane at 128 registers (round-2 verdict), and a scratch reload in
-    // the flush path serialises the stores with their own completion; they are gone.  (Sides above 1024 take the streaming
-    // sweep from 64-96 sources up as before; smaller fp32 batches there run one row per lane in rounds of 512 rows.)
-    // (pick_shape's strip count where it already chose one row per lane -- small and odd-width grids keep their small
-    // workgroups --, else as many strips as the rows need, up to 8; "rows_per_lane" other than 1 is ignored for fp32 fields)
-    const int Wf = (c->opt_strips || R == 1) ? W : std::min(W * R, 8);
-    const bool multi_f = Wf * 64 < std::max(c->nx, c->ny) || c->opt_multi;
-    return multi_f ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, Wf) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, Wf);
+  const vhp::SweepPlan p = plan_for(c, n_src, sizeof(OutT) == 8);
+  c->last_kernel = p.kernel;
+  if (p.kernel != 1) return launch_batch_sweep<OutT>(c, d_src, n_src, d_out, p.kernel == 4);
+  if constexpr (sizeof(OutT) == 4) {  // (fp32 fields: only the one-row-per-lane builds exist, and the plan asks for no other)
+    return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p);
   } else {
-    switch (R) {
-      case 1: return multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, W) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, W);
-      case 2: return multi ? launch_sweep_t<2, true, OutT>(c, d_src, n_src, d_out, W) : launch_sweep_t<2, false, OutT>(c, d_src, n_src, d_out, W);
-      default: return multi ? launch_sweep_t<4, true, OutT>(c, d_src, n_src, d_out, W) : launch_sweep_t<4, false, OutT>(c, d_src, n_src, d_out, W);
+    switch (p.R) {
+      case 1: return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p);
+      case 2: return p.multi ? launch_sweep_t<2, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<2, false, OutT>(c, d_src, n_src, d_out, p);
+      default: return p.multi ? launch_sweep_t<4, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<4, false, OutT>(c, d_src, n_src, d_out, p);
     }
   }
+}
+
+// The host-buffer sweeps: the sources checked on the host, then slices of at most ~1 GiB of output through the context's
+// scratch (d_src / d_out) -- copy in, launch(n), copy out, synchronise.
+template <typename Launch>
+int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t esz, void* out_host, Launch launch) {
+  for (int s = 0; s < n_src; ++s)
+    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
+      return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
+  if (n_src == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  const size_t field = (size_t)ctx->nx * ctx->ny * esz;
+  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / field));
+  hipError_t e = grow(&ctx->d_src, &ctx->d_src_cap, (size_t)slice * 2 * sizeof(int32_t), false, ctx->stream);
+  if (e == hipSuccess) e = grow(&ctx->d_out, &ctx->d_out_cap, (size_t)slice * field, false, ctx->stream);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
+  for (int s0 = 0; s0 < n_src; s0 += slice) {
+    const int n = std::min(slice, n_src - s0);
+    VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = launch(n);
+    if (rc != VHP_OK) return rc;
+    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * field, ctx->d_out, (size_t)n * field, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return VHP_OK;
 }
 
 int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
@@ -543,12 +435,8 @@ int vhp_destroy(vhp_ctx* ctx) {
   DeviceGuard guard(ctx->device);
   hipStreamSynchronize(ctx->stream);
   free_map(ctx);
-  if (ctx->d_src) hipFree(ctx->d_src);
-  if (ctx->d_out) hipFree(ctx->d_out);
-  if (ctx->d_bnd) hipFree(ctx->d_bnd);
-  if (ctx->d_order) hipFree(ctx->d_order);
-  if (ctx->d_lat_order) hipFree(ctx->d_lat_order);
-  if (ctx->d_pool) hipFree(ctx->d_pool);
+  for (void* p : {(void*)ctx->d_src, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
+    if (p) (void)hipFree(p);
   for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto& pr : ctx->event_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (ctx->d_err) hipFree(ctx->d_err);
@@ -640,40 +528,12 @@ int vhp_sweep_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int variant,
   if (!ctx || !src_xy || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch: bad argument");
   if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch: no map set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
-  for (int s = 0; s < n_src; ++s)
-    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
-      return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
-  if (n_src == 0) return VHP_OK;
-  VHP_ON_DEVICE(ctx);
   // (the library's own scratch holds packed fields and is copied out packed: "field_stride" is a property of a caller's device buffer)
   struct PackedHere { long long& v; long long keep; ~PackedHere() { v = keep; } } packed{ctx->opt_field_stride, ctx->opt_field_stride};
   ctx->opt_field_stride = 0;
-  const size_t esz = dtype == VHP_F64 ? 8 : 4;
-  const size_t cells = (size_t)ctx->nx * ctx->ny;
-  // bound device scratch: process the batch in slices of at most ~1 GiB of output
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / (cells * esz)));
-  if (ctx->d_src_cap < (size_t)slice) {
-    if (ctx->d_src) hipFree(ctx->d_src);
-    ctx->d_src = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_src, (size_t)slice * 2 * sizeof(int32_t)));
-    ctx->d_src_cap = slice;
-  }
-  if (ctx->d_out_cap < (size_t)slice * cells * esz) {
-    if (ctx->d_out) hipFree(ctx->d_out);
-    ctx->d_out = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_out, (size_t)slice * cells * esz));
-    ctx->d_out_cap = (size_t)slice * cells * esz;
-  }
-  for (int s0 = 0; s0 < n_src; s0 += slice) {
-    const int n = std::min(slice, n_src - s0);
-    VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    int rc = vhp_sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out);
-    if (rc != VHP_OK) return rc;
-    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * cells * esz, ctx->d_out, (size_t)n * cells * esz,
-                           hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return vhp_sync(ctx);
+  const int rc = stage_batch(ctx, "vhp_sweep_batch", src_xy, n_src, dtype == VHP_F64 ? 8 : 4, out_host,
+                             [&](int n) { return vhp_sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out); });
+  return rc == VHP_OK && n_src > 0 ? vhp_sync(ctx) : rc;
 }
 
 int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
@@ -682,12 +542,7 @@ int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
   if (src_x < 0 || src_y < 0 || src_x >= ctx->nx || src_y >= ctx->ny) return fail(ctx, VHP_ERR_SOURCE_OOB, "source outside the grid");
   VHP_ON_DEVICE(ctx);
   const size_t cells = (size_t)ctx->nx * ctx->ny;
-  if (ctx->d_out_cap < cells * 8) {
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    ctx->d_out = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_out, cells * 8));
-    ctx->d_out_cap = cells * 8;
-  }
+  VHP_HIP(grow(&ctx->d_out, &ctx->d_out_cap, cells * 8, false, ctx->stream));
   double* d = static_cast<double*>(ctx->d_out);
   const unsigned blocks = (unsigned)((cells + 255) / 256);
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
@@ -746,74 +601,30 @@ int vhp_sweep_batch_variant(vhp_ctx* ctx, const int32_t* src_xy, int n_src, doub
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(fac > 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_variant: bad argument");
   if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_variant: no map set");
   if (std::max(ctx->nx, ctx->ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant sweeps: grid side above 4096");
-  for (int s = 0; s < n_src; ++s)
-    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
-      return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
-  if (n_src == 0) return VHP_OK;
-  VHP_ON_DEVICE(ctx);
-  const size_t cells = (size_t)ctx->nx * ctx->ny;
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / (cells * 8)));
-  if (ctx->d_src_cap < (size_t)slice) {
-    if (ctx->d_src) hipFree(ctx->d_src);
-    ctx->d_src = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_src, (size_t)slice * 2 * sizeof(int32_t)));
-    ctx->d_src_cap = slice;
-  }
-  if (ctx->d_out_cap < (size_t)slice * cells * 8) {
-    if (ctx->d_out) hipFree(ctx->d_out);
-    ctx->d_out = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_out, (size_t)slice * cells * 8));
-    ctx->d_out_cap = (size_t)slice * cells * 8;
-  }
-  for (int s0 = 0; s0 < n_src; s0 += slice) {
-    const int n = std::min(slice, n_src - s0);
-    VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = variant_launch_sweep(ctx, ctx->d_src, n, alpha, fac, static_cast<double*>(ctx->d_out));
-    if (rc != VHP_OK) return rc;
-    VHP_HIP(hipMemcpyAsync(out_host + (size_t)s0 * cells, ctx->d_out, (size_t)n * cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return VHP_OK;
+  return stage_batch(ctx, "vhp_sweep_batch_variant", src_xy, n_src, 8, out_host,
+                     [&](int n) { return variant_launch_sweep(ctx, ctx->d_src, n, alpha, fac, static_cast<double*>(ctx->d_out)); });
 }
 
 int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double offset, double* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(offset >= 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_offset: bad argument");
   if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_offset: no map set");
   if (std::max(ctx->nx, ctx->ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "offset sweeps: grid side above 4096");
-  for (int s = 0; s < n_src; ++s)
-    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
-      return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
-  if (n_src == 0) return VHP_OK;
-  VHP_ON_DEVICE(ctx);
   const size_t cells = (size_t)ctx->nx * ctx->ny;
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / (cells * 8)));
-  if (ctx->d_src_cap < (size_t)slice) {
-    if (ctx->d_src) hipFree(ctx->d_src);
-    ctx->d_src = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_src, (size_t)slice * 2 * sizeof(int32_t)));
-    ctx->d_src_cap = slice;
-  }
-  if (ctx->d_out_cap < (size_t)slice * cells * 8) {
-    if (ctx->d_out) hipFree(ctx->d_out);
-    ctx->d_out = nullptr;
-    VHP_HIP(hipMalloc(&ctx->d_out, (size_t)slice * cells * 8));
-    ctx->d_out_cap = (size_t)slice * cells * 8;
-  }
   const size_t lds = (size_t)3 * (std::max(ctx->nx, ctx->ny) + 1) * sizeof(double);
   auto k = vhp::variant::vhp_offset_sweep;
-  hipError_t e = raise_lds_limit(ctx, reinterpret_cast<const void*>(k), lds);
-  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("offset sweep: ") + hipGetErrorString(e));
-  for (int s0 = 0; s0 < n_src; s0 += slice) {
-    const int n = std::min(slice, n_src - s0);
-    VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  bool raised = false;
+  return stage_batch(ctx, "vhp_sweep_batch_offset", src_xy, n_src, 8, out_host, [&](int n) -> int {
+    if (!raised) {  // (once per call, on the context's device)
+      hipError_t e = raise_lds_limit(ctx, reinterpret_cast<const void*>(k), lds);
+      if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("offset sweep: ") + hipGetErrorString(e));
+      raised = true;
+    }
     VHP_HIP(hipMemsetAsync(ctx->d_out, 0, (size_t)n * cells * 8, ctx->stream));  // a freshly reset() solver
     hipLaunchKernelGGL(k, dim3((unsigned)(4 * n)), dim3(1024), lds, ctx->stream, ctx->nx, ctx->ny, ctx->d_occ, ctx->d_src,
                        static_cast<double*>(ctx->d_out), (long long)cells, offset, ctx->d_err);
     VHP_HIP(hipGetLastError());
-    VHP_HIP(hipMemcpyAsync(out_host + (size_t)s0 * cells, ctx->d_out, (size_t)n * cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return VHP_OK;
+    return VHP_OK;
+  });
 }
 
 int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end_y, double threshold, double alpha,
@@ -1092,19 +903,12 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
   std::string msg;
   vhp::DevMap pm = dev_map(ctx);
   {
-    int R, W;
-    bool multi;
-    pick_shape(ctx, std::max(ctx->nx, ctx->ny), &R, &W, &multi);
-    hipError_t eb = vhp::attach_round_scratch(pm, W * 64 * R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
-    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
-    ctx->pl.R = R;
-    ctx->pl.W = W;
-    ctx->pl.multi = multi;
-    ctx->pl.raise_lds = [ctx](const void* fn, size_t bytes) { return raise_lds_limit(ctx, fn, bytes); };
     // one source per sweep: the latency sweep wherever a batch of one would take it (94 against 67 us per sweep at 690^2)
+    vhp::SweepPlan plan;
+    hipError_t eb = plan_planner(ctx, pm, 1, 4, &plan);
+    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
     ctx->pl.lat_sweep = nullptr;
-    ctx->last_kernel = use_lat_kernel(ctx, 1) ? 4 : 1;  // (vhp_last_sweep_kernel after a solve: what swept its iterations)
-    if (use_lat_kernel(ctx, 1))
+    if (plan.kernel == 4)
       ctx->pl.lat_sweep = [ctx](const int32_t* pivots, const int* nb, const int* done, const int* rec, double* out, bool dark_unwritten) {
         ctx->lat_src_index = nb;
         ctx->lat_skip = done;
@@ -1157,19 +961,12 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
   std::string msg;
   vhp::DevMap pm = dev_map(ctx);
   {
-    int R, W;
-    bool multi;
-    pick_shape(ctx, std::max(ctx->nx, ctx->ny), &R, &W, &multi);
-    hipError_t eb = vhp::attach_round_scratch(pm, W * 64 * R, (size_t)4 * vhp::kSpecMaxK, &ctx->d_bnd, &ctx->d_bnd_cap);
-    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
-    ctx->pl.R = R;
-    ctx->pl.W = W;
-    ctx->pl.multi = multi;
-    ctx->pl.raise_lds = [ctx](const void* fn, size_t bytes) { return raise_lds_limit(ctx, fn, bytes); };
     // k sources per launch: the latency sweep (8 k workgroups) wherever a batch of k would take it
+    vhp::SweepPlan plan;
+    hipError_t eb = plan_planner(ctx, pm, k, (size_t)4 * vhp::kSpecMaxK, &plan);
+    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
     ctx->pl.lat_sweep_k = nullptr;
-    ctx->last_kernel = use_lat_kernel(ctx, k) ? 4 : 1;
-    if (use_lat_kernel(ctx, k))
+    if (plan.kernel == 4)
       ctx->pl.lat_sweep_k = [ctx](const int32_t* cand, int n, const int* slot_base, const int* run_if, const int* done, double* cache, bool dark_unwritten) {
         ctx->lat_skip = done;
         ctx->lat_slot_base = slot_base;
