@@ -131,6 +131,34 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
                                   int k, int mode, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy,
                                   uint32_t* n_pivots, int32_t* stats);
 
+/* Many planner queries on one map in one call: Q independent solve()s, each giving exactly what vhp_planner_solve gives for it
+ * alone (status, pivots, labels, union, last local field -- bit for bit).  queries: Q x {start_x, start_y, end_x, end_y} (field
+ * coordinates); thresholds: Q doubles; max_iter shared.  status[q]: what vhp_planner_solve would return for query q alone (the four
+ * validation codes, checked in the reference's order; VHP_OK, VHP_ERR_MAX_ITER, VHP_ERR_NOTHING_LIT); n_pivots[q]: its
+ * nb_of_sources_ (0 for a query that failed validation).  These per-query outcomes go only into status[]: the call then returns
+ * VHP_OK (vhp_last_error names the first query that failed validation).  The call itself fails with VHP_ERR_ARG (n_queries outside
+ * 1..64, a null queries / thresholds / status / n_pivots, max_iter > 2^24), VHP_ERR_NO_MAP or VHP_ERR_HIP.
+ * One iteration serves every query still running: ONE latency-sweep launch whose source g is query g's current pivot, then ONE
+ * epilogue launch over all their states; the host polls every 8 iterations.  The queries run in groups of G, one group after the
+ * other: G is the largest of 32, 16, 8, 4, 2 for which a sweep of G sources takes the latency sweep (vhp_last_sweep_kernel's rule)
+ * and G queries' state -- 28 bytes per cell and the pivot list per query -- fits in a quarter of the free device memory, else 1;
+ * vhp_set_option "planner_batch_group" (0 automatic, 1..32) caps it.  Where not even one source takes the latency sweep, every query
+ * runs on the front sweep alone.  No result depends on G.  The results of ALL the batch's queries stay in device memory (28 bytes per
+ * cell per query) until the next batch solve or vhp_set_map; the batch's state is its own: vhp_planner_results_device still returns
+ * the last plain solve's.  vhp_last_elapsed_ms times the whole call; vhp_last_sweep_kernel says what swept its iterations (4 or 1).
+ * vhp_planner_batch_results_device hands out query q's device arrays (the layout of vhp_planner_results_device), and
+ * vhp_planner_batch_results copies them to the host in the layout of vhp_planner_solve's outputs (pivots_xy: n_pivots[q] + 1
+ * pairs); any output pointer may be NULL.  Both return VHP_ERR_ARG for q outside 0..Q-1, for a query that failed validation, and
+ * before any batch has been solved since the last vhp_set_map.
+ * vhp_planner_batch_group (beyond the three calls the batch was specified with): the G the last batch solve ran with, 0 before any. */
+int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* thresholds, int n_queries, uint64_t max_iter,
+                            int32_t* status, uint32_t* n_pivots);
+int vhp_planner_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global,
+                                     const double** vis_local, const int32_t** pivots_xy);
+int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local,
+                              int32_t* pivots_xy);
+int vhp_planner_batch_group(const vhp_ctx* ctx);
+
 /* Replaces reconstructPath() (solver.cpp:1183-1213): walks came_from -> pivots from
  * `end` until the label repeats; writes the path start-first into path_xy (capacity
  * cap points), its point count into *n_path, the summed eval_d length into *length.
@@ -198,7 +226,8 @@ int vhp_timing_collect(vhp_ctx* ctx, float* ms_out, int cap, int* n);
  * round, so that the longest units share their CU with the shortest of the round), "field_stride" (elements from one field of a DEVICE-pointer batch to the next;
  * 0 = nx * ny, packed; a value below nx * ny makes vhp_sweep_batch_device fail with VHP_ERR_ARG; the host-buffer entry points
  * ignore it -- their results are packed --, the queue variant refuses it, and vhp_set_map resets it to 0),
- * "alloc_budget_pct" (vhp_alloc_output below).  The
+ * "alloc_budget_pct" (vhp_alloc_output below), "planner_batch_group" (0 automatic, 1..32: queries per group of
+ * vhp_planner_solve_batch at most).  The
  * results never depend on these; only the schedule (and, with field_stride, the placement of the fields) does. */
 int vhp_set_option(vhp_ctx* ctx, const char* key, long long value);
 /* Which kernel the last batch sweep of this context launched: 1 = front sweep (vhp_sweep_fronts),

@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "vhp_multi_create", "vhp_multi_destroy", "vhp_multi_last_error", "vhp_multi_devices", "vhp_multi_context", "vhp_multi_shard_bounds",
     "vhp_multi_set_map", "vhp_multi_sweep_batch", "vhp_multi_allgather_fields", "vhp_multi_allgather_plan", "vhp_multi_use_rccl",
     "vhp_union_fields_device", "vhp_union_partials_device", "vhp_multi_union_fields",
+    "vhp_planner_solve_batch", "vhp_planner_batch_results_device", "vhp_planner_batch_results", "vhp_planner_batch_group",
 )
 
 
@@ -90,6 +91,10 @@ def load_library():
     lib.vhp_planner_solve_speculative.argtypes = [vp, i32, i32, i32, i32, f64, u64, i32, i32, vp, vp, vp, vp, C.POINTER(u32), vp]
     lib.vhp_planner_solve_device.argtypes = [vp, i32, i32, i32, i32, f64, u64, C.POINTER(u32)]
     lib.vhp_planner_results_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.vhp_planner_solve_batch.argtypes = [vp, vp, vp, i32, u64, vp, vp]
+    lib.vhp_planner_batch_results_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.vhp_planner_batch_results.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.vhp_planner_batch_group.argtypes = [vp]
     lib.vhp_sweep_batch_variant.argtypes = [vp, vp, i32, f64, f64, vp]
     lib.vhp_planner_solve_variant.argtypes = [vp, i32, i32, i32, i32, f64, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_sweep_batch_offset.argtypes = [vp, vp, i32, f64, vp]
@@ -283,6 +288,44 @@ class Context:
             self._check(self.lib.vhp_planner_results_device(self.h, *[C.byref(q) for q in p]))
             ptrs = dict(labels=p[0].value, vis_global=p[1].value, vis_local=p[2].value, pivots=p[3].value)
         return rc, npiv.value, ptrs
+
+    def planner_solve_batch(self, queries, thresholds, max_iter, outputs=True):
+        """vhp_planner_solve_batch: Q independent planner_solve calls on this map in one call.  queries: [Q, 4] (start_x, start_y,
+        end_x, end_y), field coordinates; thresholds: Q values or one for all.  Returns one dict per query with planner_solve's keys
+        and dtypes (outputs=False: status and n_pivots only).  A query that failed validation has pivots [[0, 0]] and None for
+        came_from, vis_global and vis_local, as it has no results."""
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1, 4)
+        n = len(q)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float64), (n,)))
+        st = np.zeros(n, np.int32)
+        npiv = np.zeros(n, np.uint32)
+        self._check(self.lib.vhp_planner_solve_batch(self.h, _ptr(q), _ptr(thr), n, int(max_iter), _ptr(st), _ptr(npiv)))
+        out = []
+        for k in range(n):
+            r = dict(status=int(st[k]), n_pivots=int(npiv[k]))
+            if outputs:
+                solved = r["status"] in (VHP_OK, VHP_ERR_MAX_ITER, VHP_ERR_NOTHING_LIT)
+                piv = np.zeros((r["n_pivots"] + 1, 2), np.int32)
+                came = vg = vl = None
+                if solved:
+                    came = np.empty((self.ny, self.nx), np.uint64)
+                    vg = np.empty((self.ny, self.nx), np.float64)
+                    vl = np.empty((self.ny, self.nx), np.float64)
+                    self._check(self.lib.vhp_planner_batch_results(self.h, k, _ptr(came), _ptr(vg), _ptr(vl), _ptr(piv)))
+                r.update(came_from=came, vis_global=vg, vis_local=vl, pivots=piv)
+            out.append(r)
+        return out
+
+    def planner_batch_results_device(self, q):
+        """Raw device pointers of query q of the last planner_solve_batch: labels uint32 [ny, nx], vis_global / vis_local float64
+        [ny, nx], pivots int32 [n_pivots + 1, 2] (vhp_planner_batch_results_device)."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._check(self.lib.vhp_planner_batch_results_device(self.h, int(q), *[C.byref(v) for v in p]))
+        return dict(labels=p[0].value, vis_global=p[1].value, vis_local=p[2].value, pivots=p[3].value)
+
+    def planner_batch_group(self):
+        """Queries per group of the last planner_solve_batch (0: none yet)."""
+        return int(self.lib.vhp_planner_batch_group(self.h))
 
     def sweep_batch_variant(self, sources, alpha=1.0, fac=1.0):
         """MATLAB-flavoured sweep (getAccessibilityMap.m): fields [n, ny, nx] float64."""

@@ -21,6 +21,7 @@
 #include "vhp_choice.hpp"
 #include "vhp_sweep.hip.h"
 #include "vhp_planner.hip.h"
+#include "vhp_planner_batch.hip.h"
 #include "vhp_queue.hip.h"
 #include "vhp_variant.hip.h"
 #include "vhp_union.hip.h"
@@ -94,6 +95,8 @@ struct vhp_ctx {
 
   vhp::PlannerState pl;  // device-resident planner state
   vhp::SpecState spec;   // field cache of the speculative planner
+  vhp::BatchState batch; // the batch planner's queries (vhp_planner_solve_batch), apart from pl
+  int opt_planner_batch_group = 0;  // queries per group of a batch solve at most (0: automatic, planner_batch_group_size)
   vhp::QueueScratch qs;  // scratch of the queue-variant sweep
 };
 
@@ -173,6 +176,7 @@ void free_map(vhp_ctx* c) {
   c->pl.h_occ = nullptr;
   vhp::planner_free(c->pl);
   vhp::spec_free(c->spec);
+  vhp::batch_free(c->batch);
   vhp::queue_scratch_free(c->qs);
   c->nx = c->ny = 0;
 }
@@ -397,6 +401,41 @@ int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   ctx->nx = nx;
   ctx->ny = ny;
+  return VHP_OK;
+}
+
+// G of a batch solve (vhp_planner_solve_batch): the largest of 32, 16, 8, 4, 2 for which a launch of G sources takes the latency sweep
+// and G queries' state fits in a quarter of the free device memory, else 1 -- capped by "planner_batch_group" --; 0 where even one
+// source does not take the latency sweep (the queries then run one by one on the front sweep).
+int planner_batch_group_size(const vhp_ctx* c, uint64_t max_iter) {
+  if (plan_for(c, 1, true).kernel != 4) return 0;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+  const size_t per_query = vhp::kBatchBytesPerCell * (size_t)c->nx * c->ny + 2 * (size_t)(max_iter + 2) * sizeof(int32_t);
+  int g = 1;
+  for (int G = vhp::kBatchMaxGroup; G > 1; G /= 2)
+    if (plan_for(c, G, true).kernel == 4 && (size_t)G * per_query <= free_b / 4) { g = G; break; }
+  return c->opt_planner_batch_group > 0 ? std::min(g, c->opt_planner_batch_group) : g;
+}
+
+// The batch planner's front sweep of one query (where the latency sweep does not take a single source): vhp_planner_sweep, as
+// planner_solve launches it.
+template <int R, bool MULTI>
+hipError_t launch_batch_fronts(vhp_ctx* c, const vhp::DevMap& m, const vhp::PlannerDev& d, int W) {
+  const size_t lds = vhp::sweep_lds_bytes(R, W, MULTI);
+  auto k = vhp::vhp_planner_sweep<R, MULTI>;
+  if (hipError_t e = raise_lds_limit(c, reinterpret_cast<const void*>(k), lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(4), dim3(128 * W), lds, c->stream, m, d);
+  return hipGetLastError();
+}
+
+// The last batch's slot of query q, or an error for the _results entry points.
+int batch_slot(vhp_ctx* ctx, const char* who, int q, int* slot) {
+  const vhp::BatchState& b = ctx->batch;
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": no batch solved on this map");
+  if (q < 0 || q >= (int)b.slot_of.size()) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query index out of range");
+  if (b.slot_of[q] < 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query " + std::to_string(q) + " failed validation and has no results");
+  *slot = b.slot_of[q];
   return VHP_OK;
 }
 
@@ -734,6 +773,7 @@ int vhp_set_option(vhp_ctx* ctx, const char* key, long long value) {
   else if (k == "pool_busy_cap") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_busy_cap: 0 (automatic) .. 16"); ctx->opt_pool_busy_cap = v; }
   else if (k == "pool_contexts") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_contexts: 0 (automatic) .. 16"); ctx->opt_pool_contexts = v; }
   else if (k == "pool_static_round") { if (v < 0 || v > 2) return fail(ctx, VHP_ERR_ARG, "pool_static_round: 0, 1 or 2"); ctx->opt_pool_static_round = v; }
+  else if (k == "planner_batch_group") { if (v < 0 || v > vhp::kBatchMaxGroup) return fail(ctx, VHP_ERR_ARG, "planner_batch_group: 0 (automatic) .. 32"); ctx->opt_planner_batch_group = v; }
   else if (k == "alloc_budget_pct") { if (v < 1 || v > 90) return fail(ctx, VHP_ERR_ARG, "alloc_budget_pct: 1 .. 90 (per cent of the free device memory)"); ctx->opt_alloc_budget_pct = v; }
   else return fail(ctx, VHP_ERR_ARG, "vhp_set_option: unknown key '" + k + "'");
   return VHP_OK;
@@ -1007,6 +1047,78 @@ int vhp_planner_results_device(vhp_ctx* ctx, const uint32_t** labels, const doub
   if (vis_local) *vis_local = ctx->pl.vis_local_out ? ctx->pl.vis_local_out : ctx->pl.vis_local;
   if (pivots_xy) *pivots_xy = ctx->pl.pivots;
   return VHP_OK;
+}
+
+int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* thresholds, int n_queries, uint64_t max_iter,
+                            int32_t* status, uint32_t* n_pivots) {
+  if (!ctx) return VHP_ERR_ARG;
+  if (n_queries < 1 || n_queries > vhp::kBatchMaxQueries) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_batch: n_queries outside 1..64");
+  if (!queries || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_batch: null array");
+  if (max_iter > (1u << 24)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
+  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_batch: no map set");
+  VHP_ON_DEVICE(ctx);
+  vhp::DevMap pm = dev_map(ctx);
+  vhp::BatchState& b = ctx->batch;
+  const int G = planner_batch_group_size(ctx, max_iter);
+  b.lat_sweep = nullptr;
+  b.front_sweep = nullptr;
+  if (G > 0) {
+    b.lat_sweep = [ctx](const int32_t* cand, int n, double* out) {
+      ctx->lat_slot_base = reinterpret_cast<const int*>(ctx->batch.n_done + 1);   // (a zero: field g of the launch is query g's)
+      ctx->lat_dark_unwritten = true;
+      const long long stride = ctx->opt_field_stride;
+      ctx->opt_field_stride = 0;  // (the queries' local fields are packed)
+      const bool timing = ctx->timing;
+      ctx->timing = false;  // (as in vhp_planner_solve's loop)
+      const hipError_t e = launch_batch_sweep<double>(ctx, cand, n, out, true);
+      ctx->timing = timing;
+      ctx->opt_field_stride = stride;
+      ctx->lat_slot_base = nullptr;
+      ctx->lat_dark_unwritten = false;
+      return e;
+    };
+    ctx->last_kernel = 4;
+  } else {
+    const vhp::SweepPlan plan = plan_for(ctx, 1, true);
+    hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
+    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d) {
+      switch (plan.R) {
+        case 1: return plan.multi ? launch_batch_fronts<1, true>(ctx, pm, d, plan.W) : launch_batch_fronts<1, false>(ctx, pm, d, plan.W);
+        case 2: return plan.multi ? launch_batch_fronts<2, true>(ctx, pm, d, plan.W) : launch_batch_fronts<2, false>(ctx, pm, d, plan.W);
+        default: return plan.multi ? launch_batch_fronts<4, true>(ctx, pm, d, plan.W) : launch_batch_fronts<4, false>(ctx, pm, d, plan.W);
+      }
+    };
+    ctx->last_kernel = 1;
+  }
+  std::string msg;
+  const int rc = vhp::planner_solve_batch(b, pm, ctx->d_occ, ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream, ctx->ev0,
+                                          ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg);
+  ctx->timed = true;
+  if (!msg.empty()) ctx->err = msg;
+  return rc;
+}
+
+int vhp_planner_batch_group(const vhp_ctx* ctx) { return ctx && ctx->batch.solved ? ctx->batch.group : 0; }
+
+int vhp_planner_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
+                                     const int32_t** pivots_xy) {
+  if (!ctx) return VHP_ERR_ARG;
+  int k = 0;
+  if (int rc = batch_slot(ctx, "vhp_planner_batch_results_device", q, &k); rc != VHP_OK) return rc;
+  vhp::batch_results_device(ctx->batch, k, labels, vis_global, vis_local, pivots_xy);
+  return VHP_OK;
+}
+
+int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
+  if (!ctx) return VHP_ERR_ARG;
+  int k = 0;
+  if (int rc = batch_slot(ctx, "vhp_planner_batch_results", q, &k); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  std::string msg;
+  const int rc = vhp::batch_results_host(ctx->batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
+  if (rc != VHP_OK) ctx->err = msg;
+  return rc;
 }
 
 // eval_d of visibilityBasedSolver.h:112-115 (host side, used only for the path length)

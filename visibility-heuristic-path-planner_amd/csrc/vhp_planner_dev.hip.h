@@ -121,9 +121,10 @@ constexpr int kSpecPartials = kEpilogueBlocks * kEpilogueWaves;  // the speculat
 // THREADS: the workgroup's size; block of n_blocks: which share of the cells is this workgroup's.  sweeps_done (or nullptr): the
 // iteration's sweep runs in the SAME launch (vhp_lat.hip vhp_planner_iteration): its workgroups count themselves in there when their
 // stores are out, and this workgroup may read the local field only after all n_sweeps of them have -- the loads that do not depend on
-// the sweep (the union, the labels, the other local field) are on their way by then.
+// the sweep (the union, the labels, the other local field) are on their way by then.  Returns true in the one thread that has just
+// picked the next pivot and written d.rec (the batch planner's epilogue goes on from there: vhp_planner_batch.hip.h), false in all others.
 template <int THREADS>
-__device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const PlannerDev& d, int block, int n_blocks, const unsigned* sweeps_done, unsigned n_sweeps) {
+__device__ __forceinline__ bool planner_epilogue_body(int nx, int ny, const PlannerDev& d, int block, int n_blocks, const unsigned* sweeps_done, unsigned n_sweeps) {
   constexpr int kWaves = THREADS / 64;
   __shared__ PlannerKey slots[kWaves];
   const size_t cells = (size_t)nx * ny;
@@ -154,7 +155,7 @@ __device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const Plan
   const int done = d.ctl->done, nb = d.ctl->nb;
   load_rest(k0);
   if (!sweeps_done) load_local(k0);
-  if (done) return;
+  if (done) return false;
   if (sweeps_done) {
     // The sweep's workgroups are other workgroups of this launch: one lane waits for their count (an agent-scope load: they sit on
     // other CUs, behind other L2s), the workgroup's barrier, then every wavefront's acquire -- what it loads from here on is what
@@ -235,13 +236,13 @@ __device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const Plan
     }
   }
   __syncthreads();
-  if (!is_last) return;
+  if (!is_last) return false;
   // Wavefront 0 alone, on registers: the partials (agent-scope loads: other CUs wrote them), the loop condition's cell (written by
   // some workgroup of this kernel) and the iteration count are asked for together; the minimum of (h, rank) by DPP; lane 0 stores
   // the pick -- ls_ = top(); ++nb_of_sources_; lightSources_[nb] = ls_; the loop condition (solver.cpp:127-141).
   // (Until round 5: a partial per thread, a butterfly of ds_bpermute per wavefront, a barrier, one thread over the wavefronts'
   // minima and then the pick's trips to memory one after the other.)
-  if (wave != 0) return;
+  if (wave != 0) return false;
   const int lane = (int)threadIdx.x;
   const double ge = __longlong_as_double((long long)__hip_atomic_load(
       reinterpret_cast<const unsigned long long*>(d.vis_global + (size_t)d.end_y * nx + d.end_x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -267,7 +268,7 @@ __device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const Plan
   const unsigned long long holders = __ballot(k.h == hmin && k.rank == rmin);
   const int wl = holders ? __ffsll((long long)holders) - 1 : 0;
   const int wx = __builtin_amdgcn_readlane(k.x, wl), wy = __builtin_amdgcn_readlane(k.y, wl);  // (-1: nothing reached the threshold)
-  if (lane != 0) return;
+  if (lane != 0) return false;
   d.ticket[0] = 0;  // for the next iteration (kernels of one stream run in order)
   d.ticket[1] = 0;  // (... and the count of the sweep's workgroups, where the sweep runs in the epilogue's launch)
   d.ctl->iters = iters + 1;
@@ -275,7 +276,7 @@ __device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const Plan
     d.ctl->status = VHP_ERR_NOTHING_LIT;
     d.ctl->done = 1;
     d.rec[0] = 1;
-    return;
+    return true;
   }
   const int nbn = nb + 1;
   int px = wx, py = wy, status = -1;
@@ -286,6 +287,7 @@ __device__ __forceinline__ void planner_epilogue_body(int nx, int ny, const Plan
   d.pivots[2 * nbn + 1] = py;
   if (status >= 0) { d.ctl->status = status; d.ctl->done = 1; }
   *reinterpret_cast<int4*>(d.rec) = make_int4(status >= 0 ? 1 : 0, nbn, px, py);
+  return true;
 }
 
 }  // namespace vhp
