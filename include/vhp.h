@@ -89,6 +89,25 @@ int vhp_sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int
  * (VHP_ERR_SOURCE_OOB if any source of an earlier *_device call was out of range). */
 int vhp_sync(vhp_ctx* ctx);
 
+/* A stack of maps: n_maps maps of one nx x ny, map k at occ + k*nx*ny (1 = free, row-major), packed like vhp_set_map's map.
+ * Context state of its own: vhp_set_maps replaces the previous stack and leaves the single map of vhp_set_map, the planner's
+ * state and the batch planner's as they are (and vhp_set_map leaves the stack); vhp_destroy frees it.  n_maps < 1, a null
+ * pointer or a side < 1: VHP_ERR_ARG; a side above VHP_MAX_SIDE: VHP_ERR_TOO_LARGE; a failed allocation: VHP_ERR_HIP, with
+ * no stack set.  "field_stride" is left as it is. */
+int vhp_set_maps(vhp_ctx* ctx, const uint8_t* occ, int n_maps, int nx, int ny);
+/* Same, the uint8 maps already resident in device memory. */
+int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, int ny);
+/* Replaces computeVisibility() (solver.cpp:570-696) run on a different environment per source: field i is the sweep from
+ * src_xy[2i..2i+1] on map map_idx[i] of the stack, bit for bit what vhp_set_map(that map) + vhp_sweep_batch(VHP_SWEEP_FULL,
+ * dtype) gives.  Output layout, zero cells and n_src as in vhp_sweep_batch.  Always the front sweep (vhp_last_sweep_kernel
+ * reports 1); the shape options apply as in vhp_sweep_batch, "kernel" is ignored.  A source outside the grid or a map index
+ * outside 0..n_maps-1 leaves its field 0, the others are swept, and the call returns VHP_ERR_SOURCE_OOB.  No stack set:
+ * VHP_ERR_NO_MAP. */
+int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host);
+/* Device-resident form, as vhp_sweep_batch_device ("field_stride" and the alignment rule checked against the stack's nx*ny):
+ * a rejected source's field is not written, and vhp_sync() reports VHP_ERR_SOURCE_OOB. */
+int vhp_sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out);
+
 /* Replaces solve() (solver.cpp:76-160) incl. updateVisibility() (:379-565), the
  * heap / top() arg-min (visibilityBasedSolver.h:16-21,138) and resetQueue().
  * Coordinates are FIELD coordinates (the mode-2 y flip of solver.cpp:83-86 is the

@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "vhp_multi_set_map", "vhp_multi_sweep_batch", "vhp_multi_allgather_fields", "vhp_multi_allgather_plan", "vhp_multi_use_rccl",
     "vhp_union_fields_device", "vhp_union_partials_device", "vhp_multi_union_fields",
     "vhp_planner_solve_batch", "vhp_planner_batch_results_device", "vhp_planner_batch_results", "vhp_planner_batch_group",
+    "vhp_set_maps", "vhp_set_maps_device", "vhp_sweep_maps_batch", "vhp_sweep_maps_batch_device",
 )
 
 
@@ -85,6 +86,10 @@ def load_library():
     lib.vhp_sweep_batch.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.vhp_sweep_batch_device.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.vhp_sync.argtypes = [vp]
+    lib.vhp_set_maps.argtypes = [vp, vp, i32, i32, i32]
+    lib.vhp_set_maps_device.argtypes = [vp, vp, i32, i32, i32]
+    lib.vhp_sweep_maps_batch.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.vhp_sweep_maps_batch_device.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_planner_solve.argtypes = [vp, i32, i32, i32, i32, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_reconstruct_path.argtypes = [vp, vp, u32, i32, i32, i32, i32, vp, u32, C.POINTER(u32), C.POINTER(f64)]
     lib.vhp_set_option.argtypes = [vp, C.c_char_p, C.c_longlong]
@@ -146,6 +151,7 @@ class Context:
         self.nx = self.ny = 0
         self.stream = 0           # the stream handle last given to set_stream (0: the default stream)
         self.field_stride = 0     # the "field_stride" option as last set (vhp_set_map resets it to 0)
+        self.n_maps = self.maps_nx = self.maps_ny = 0  # the stack of maps of set_maps
 
     def close(self):
         if getattr(self, "h", None):
@@ -184,6 +190,36 @@ class Context:
     def sweep_batch_device(self, d_src, n_src, d_out, variant=SWEEP_FULL, dtype=F64):
         """Device-resident, asynchronous on the context stream.  d_src / d_out are raw device pointers."""
         self._check(self.lib.vhp_sweep_batch_device(self.h, C.c_void_p(d_src), n_src, variant, dtype, C.c_void_p(d_out)))
+
+    def set_maps(self, occ):
+        """A stack of maps of one size, uint8 [M, ny, nx] (1 = free): state of its own, beside the map of set_map."""
+        occ = np.ascontiguousarray(occ, np.uint8)
+        if occ.ndim != 3:
+            raise ValueError("set_maps: occ must be [n_maps, ny, nx], got shape %r" % (occ.shape,))
+        m, ny, nx = occ.shape
+        self.n_maps = self.maps_nx = self.maps_ny = 0
+        self._check(self.lib.vhp_set_maps(self.h, _ptr(occ), m, nx, ny))
+        self.n_maps, self.maps_nx, self.maps_ny = m, nx, ny
+
+    def set_maps_device(self, dptr, n_maps, nx, ny):
+        """Same, the maps already in device memory (raw pointer)."""
+        self.n_maps = self.maps_nx = self.maps_ny = 0
+        self._check(self.lib.vhp_set_maps_device(self.h, C.c_void_p(dptr), n_maps, nx, ny))
+        self.n_maps, self.maps_nx, self.maps_ny = n_maps, nx, ny
+
+    def sweep_maps_batch(self, sources, map_index, dtype=F64):
+        """Host-buffer form.  sources int32 [n, 2] (x, y), map_index int32 [n] (the map of each source) -> fields [n, ny, nx]."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+        idx = np.ascontiguousarray(map_index, np.int32).reshape(-1)
+        if len(idx) != len(src):
+            raise ValueError("sweep_maps_batch: %d sources but %d map indices" % (len(src), len(idx)))
+        out = np.empty((len(src), self.maps_ny, self.maps_nx), np.float64 if dtype == F64 else np.float32)
+        self._check(self.lib.vhp_sweep_maps_batch(self.h, _ptr(src), _ptr(idx), len(src), dtype, _ptr(out)))
+        return out
+
+    def sweep_maps_batch_device(self, d_src, d_map, n_src, d_out, dtype=F64):
+        """Device-resident, asynchronous on the context stream.  d_src / d_map / d_out are raw device pointers."""
+        self._check(self.lib.vhp_sweep_maps_batch_device(self.h, C.c_void_p(d_src), C.c_void_p(d_map), n_src, dtype, C.c_void_p(d_out)))
 
     def union_fields_device(self, d_fields, n_fields, d_best, d_arg, first_index=0, dtype=F64):
         """Max-union of n_fields device-resident fields and the (lowest) source index that attains it, into d_best / d_arg (int32);

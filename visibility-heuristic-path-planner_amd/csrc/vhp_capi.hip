@@ -98,6 +98,14 @@ struct vhp_ctx {
   vhp::BatchState batch; // the batch planner's queries (vhp_planner_solve_batch), apart from pl
   int opt_planner_batch_group = 0;  // queries per group of a batch solve at most (0: automatic, planner_batch_group_size)
   vhp::QueueScratch qs;  // scratch of the queue-variant sweep
+
+  // the stack of maps of vhp_set_maps (vhp_sweep_maps_batch): state of its own, apart from the single map above
+  int maps_n = 0, maps_nx = 0, maps_ny = 0, maps_wpr = 0, maps_wpc = 0;
+  uint64_t* d_maps_rows = nullptr;  // map k's row-packed words at d_maps_rows + k*maps_ny*maps_wpr
+  uint64_t* d_maps_cols = nullptr;  // ... column-packed ones at d_maps_cols + k*maps_nx*maps_wpc
+  double* d_maps_recip = nullptr;   // one reciprocal table for max(maps_nx, maps_ny)
+  int32_t* d_map_idx = nullptr;     // host-buffer form's slice of map indices (grow)
+  size_t d_map_idx_cap = 0;
 };
 
 namespace {
@@ -161,6 +169,23 @@ vhp::DevMap dev_map(const vhp_ctx* c) {
   return m;
 }
 
+// Map 0 of the stack of vhp_set_maps; the sweep moves to map k by k times maps_stack's strides.
+vhp::DevMap stack_dev_map(const vhp_ctx* c) {
+  vhp::DevMap m = dev_map(c);
+  m.rows = c->d_maps_rows;
+  m.cols = c->d_maps_cols;
+  m.recip = c->d_maps_recip;
+  m.wpr = c->maps_wpr;
+  m.wpc = c->maps_wpc;
+  m.nx = c->maps_nx;
+  m.ny = c->maps_ny;
+  return m;
+}
+
+vhp::MapStack maps_stack(const vhp_ctx* c, const int32_t* d_map_idx) {
+  return {d_map_idx, c->maps_n, (long long)c->maps_ny * c->maps_wpr, (long long)c->maps_nx * c->maps_wpc};
+}
+
 }  // namespace
 
 namespace {
@@ -179,6 +204,26 @@ void free_map(vhp_ctx* c) {
   vhp::batch_free(c->batch);
   vhp::queue_scratch_free(c->qs);
   c->nx = c->ny = 0;
+}
+
+void free_maps(vhp_ctx* c) {
+  for (void* p : {(void*)c->d_maps_rows, (void*)c->d_maps_cols, (void*)c->d_maps_recip})
+    if (p) (void)hipFree(p);
+  c->d_maps_rows = c->d_maps_cols = nullptr;
+  c->d_maps_recip = nullptr;
+  c->maps_n = c->maps_nx = c->maps_ny = c->maps_wpr = c->maps_wpc = 0;
+}
+
+// RN(1/k) for k = 1 .. max(nx, ny) + kRecipPad, and 0 for k = 0
+std::vector<double> recip_table(int nx, int ny) {
+  const int nrec = std::max(nx, ny) + 1 + vhp::kRecipPad;
+  std::vector<double> recip(nrec);
+  recip[0] = 0.0;
+  for (int k = 1; k < nrec; ++k) {
+    volatile double d = (double)k;
+    recip[k] = 1.0 / d;  // correctly rounded IEEE division on the host
+  }
+  return recip;
 }
 
 // Grow-only device scratch: reallocated (contents not kept) when `bytes` exceeds its capacity, zeroed when new if `zero`.
@@ -210,6 +255,12 @@ void release_events(vhp_ctx* c, const EventPair& ev, hipError_t launched) {
   if (ev.first) (launched == hipSuccess ? c->timed_launches : c->event_pool).push_back(ev);
 }
 
+// The front sweep's shape for a batch of n_src sources on the stack of maps: the same plan with the kernel forced to 1.
+vhp::SweepPlan plan_for_maps(const vhp_ctx* c, int n_src, bool f64) {
+  return vhp::plan_sweep({c->maps_nx, c->maps_ny, n_src, c->n_cus, f64,
+                          {1, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, false, false, false});
+}
+
 // What sweeps a batch of n_src sources on the context's grid with its options (vhp_choice.hpp).
 vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) {
   const bool lat_ok = vhp::lat_supported(c->nx, c->ny);
@@ -232,19 +283,21 @@ hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workg
 }
 
 // The front sweep: a workgroup sweeps one quadrant with 2*W wavefronts (W strips per octant) and R rows/columns per lane;
-// fronts longer than W*64*R are swept in rounds (MULTI).
+// fronts longer than W*64*R are swept in rounds (MULTI).  With `stack`, on the stack of maps (vhp_sweep_fronts_maps).
 template <int R, bool MULTI, typename OutT>
-hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& plan) {
+hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& plan,
+                          const vhp::MapStack* stack = nullptr) {
   const int W = plan.W;
   const bool pack = c->opt_pack != 0;
   const size_t lds = vhp::sweep_lds_bytes(R, W, MULTI, pack);
   auto k = vhp::vhp_sweep_fronts<R, MULTI, OutT>;
+  auto km = vhp::vhp_sweep_fronts_maps<R, MULTI, OutT>;
   {
-    hipError_t e = raise_lds_limit(c, reinterpret_cast<const void*>(k), lds);
+    hipError_t e = raise_lds_limit(c, stack ? reinterpret_cast<const void*>(km) : reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return e;
   }
-  const long long stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)c->nx * c->ny;
-  vhp::DevMap m = dev_map(c);
+  vhp::DevMap m = stack ? stack_dev_map(c) : dev_map(c);
+  const long long stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)m.nx * m.ny;
   m.slide = plan.slide;
   hipError_t eb = vhp::attach_round_scratch(m, W * 64 * R, (size_t)n_src * vhp::kUnitsPerSource, &c->d_bnd, &c->d_bnd_cap);
   if (eb != hipSuccess) return eb;
@@ -263,13 +316,14 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
     // Packing short quadrants into one workgroup is implemented and parity-tested, but measured slower
     // on MI355X: off unless VHP_PACK is set.
     const int pack_w = (!MULTI && W == 8 && pack) ? W : 0;
-    hipLaunchKernelGGL(vhp::vhp_order_units, dim3(1), dim3(1024), 0, c->stream, d_src, n_src, c->nx, c->ny, 64 * R, pack_w, d_ord,
+    hipLaunchKernelGGL(vhp::vhp_order_units, dim3(1), dim3(1024), 0, c->stream, d_src, n_src, m.nx, m.ny, 64 * R, pack_w, d_ord,
                        d_desc);
     order = d_ord;
     desc = d_desc;
   }
   const unsigned grid = (unsigned)n_units;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, d_out, stride, c->d_err, order, desc);
+  if (stack) hipLaunchKernelGGL(km, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, *stack, d_out, stride, c->d_err, order, desc);
+  else hipLaunchKernelGGL(k, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, d_out, stride, c->d_err, order, desc);
   const hipError_t el = hipGetLastError();
   if (ev.first) (void)hipEventRecord(ev.second, c->stream);
   release_events(c, ev, el);
@@ -321,32 +375,55 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT*
   return e;
 }
 
+// The front sweep in the build of plan p's shape.
+template <typename OutT>
+hipError_t launch_fronts(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& p, const vhp::MapStack* st = nullptr) {
+  if constexpr (sizeof(OutT) == 4) {  // (fp32 fields: only the one-row-per-lane builds exist, and the plan asks for no other)
+    return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p, st);
+  } else {
+    switch (p.R) {
+      case 1: return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p, st);
+      case 2: return p.multi ? launch_sweep_t<2, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<2, false, OutT>(c, d_src, n_src, d_out, p, st);
+      default: return p.multi ? launch_sweep_t<4, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<4, false, OutT>(c, d_src, n_src, d_out, p, st);
+    }
+  }
+}
+
 template <typename OutT>
 hipError_t launch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out) {
   const vhp::SweepPlan p = plan_for(c, n_src, sizeof(OutT) == 8);
   c->last_kernel = p.kernel;
   if (p.kernel != 1) return launch_batch_sweep<OutT>(c, d_src, n_src, d_out, p.kernel == 4);
-  if constexpr (sizeof(OutT) == 4) {  // (fp32 fields: only the one-row-per-lane builds exist, and the plan asks for no other)
-    return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p);
-  } else {
-    switch (p.R) {
-      case 1: return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p);
-      case 2: return p.multi ? launch_sweep_t<2, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<2, false, OutT>(c, d_src, n_src, d_out, p);
-      default: return p.multi ? launch_sweep_t<4, true, OutT>(c, d_src, n_src, d_out, p) : launch_sweep_t<4, false, OutT>(c, d_src, n_src, d_out, p);
-    }
-  }
+  return launch_fronts<OutT>(c, d_src, n_src, d_out, p);
+}
+
+// A batch on the stack of maps: always the front sweep (vhp_sweep_fronts_maps), in plan_for_maps's shape.
+template <typename OutT>
+hipError_t launch_maps_sweep(vhp_ctx* c, const int32_t* d_src, const int32_t* d_map_idx, int n_src, OutT* d_out) {
+  const vhp::SweepPlan p = plan_for_maps(c, n_src, sizeof(OutT) == 8);
+  c->last_kernel = 1;
+  const vhp::MapStack st = maps_stack(c, d_map_idx);
+  return launch_fronts<OutT>(c, d_src, n_src, d_out, p, &st);
 }
 
 // The host-buffer sweeps: the sources checked on the host, then slices of at most ~1 GiB of output through the context's
 // scratch (d_src / d_out) -- copy in, launch(n), copy out, synchronise.
 template <typename Launch>
+int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t field, void* out_host, Launch launch);
+
+template <typename Launch>
 int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t esz, void* out_host, Launch launch) {
   for (int s = 0; s < n_src; ++s)
     if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
       return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
+  return stage_slices(ctx, who, src_xy, n_src, (size_t)ctx->nx * ctx->ny * esz, out_host, [&](int, int n) { return launch(n); });
+}
+
+// ... the slices of fields of `field` bytes: launch(s0, n) sweeps sources s0 .. s0+n-1, staged at d_src
+template <typename Launch>
+int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t field, void* out_host, Launch launch) {
   if (n_src == 0) return VHP_OK;
   VHP_ON_DEVICE(ctx);
-  const size_t field = (size_t)ctx->nx * ctx->ny * esz;
   const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / field));
   hipError_t e = grow(&ctx->d_src, &ctx->d_src_cap, (size_t)slice * 2 * sizeof(int32_t), false, ctx->stream);
   if (e == hipSuccess) e = grow(&ctx->d_out, &ctx->d_out_cap, (size_t)slice * field, false, ctx->stream);
@@ -354,7 +431,7 @@ int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src,
   for (int s0 = 0; s0 < n_src; s0 += slice) {
     const int n = std::min(slice, n_src - s0);
     VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = launch(n);
+    const int rc = launch(s0, n);
     if (rc != VHP_OK) return rc;
     VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * field, ctx->d_out, (size_t)n * field, hipMemcpyDeviceToHost, ctx->stream));
     VHP_HIP(hipStreamSynchronize(ctx->stream));
@@ -383,13 +460,8 @@ int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
     hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_occ, ctx->d_cols, nx, ny, ctx->wpc);
     VHP_HIP(hipGetLastError());
   }
-  const int nrec = std::max(nx, ny) + 1 + vhp::kRecipPad;
-  std::vector<double> recip(nrec);
-  recip[0] = 0.0;
-  for (int k = 1; k < nrec; ++k) {
-    volatile double d = (double)k;
-    recip[k] = 1.0 / d;  // correctly rounded IEEE division on the host
-  }
+  const std::vector<double> recip = recip_table(nx, ny);
+  const int nrec = (int)recip.size();
   if (vhp::lat_supported(nx, ny)) {
     const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
     VHP_HIP(hipMalloc(&ctx->d_dmap, bytes));
@@ -401,6 +473,48 @@ int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   ctx->nx = nx;
   ctx->ny = ny;
+  return VHP_OK;
+}
+
+// The stack of vhp_set_maps from the n_maps uint8 maps at src (host or device): both packed copies of every map, one launch
+// each, and the reciprocal table.  On failure the caller frees what was built.
+int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, bool from_device) {
+  struct Staged { uint8_t* p = nullptr; ~Staged() { if (p) (void)hipFree(p); } } staged;  // the host maps' device copy, for the packing only
+  const size_t cells = (size_t)n_maps * nx * ny;
+  const uint8_t* d_occ = src;
+  if (!from_device) {
+    VHP_HIP(hipMalloc(&staged.p, cells));
+    VHP_HIP(hipMemcpyAsync(staged.p, src, cells, hipMemcpyHostToDevice, ctx->stream));
+    d_occ = staged.p;
+  }
+  const int wpr = (nx + 63) / 64 + 2, wpc = (ny + 63) / 64 + 2;
+  const size_t rows_words = (size_t)n_maps * ny * wpr, cols_words = (size_t)n_maps * nx * wpc;
+  VHP_HIP(hipMalloc(&ctx->d_maps_rows, rows_words * 8));
+  VHP_HIP(hipMalloc(&ctx->d_maps_cols, cols_words * 8));
+  VHP_HIP(hipMemsetAsync(ctx->d_maps_rows, 0, rows_words * 8, ctx->stream));
+  VHP_HIP(hipMemsetAsync(ctx->d_maps_cols, 0, cols_words * 8, ctx->stream));
+  const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernels step through more maps than that)
+  {
+    const long long waves = (long long)(wpr - 2) * ny;
+    const unsigned blocks = (unsigned)((waves * 64 + 255) / 256);
+    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(blocks, gy), dim3(256), 0, ctx->stream, d_occ, ctx->d_maps_rows, n_maps, nx, ny, wpr);
+    VHP_HIP(hipGetLastError());
+  }
+  {
+    const long long waves = (long long)(wpc - 2) * nx;
+    const unsigned blocks = (unsigned)((waves * 64 + 255) / 256);
+    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(blocks, gy), dim3(256), 0, ctx->stream, d_occ, ctx->d_maps_cols, n_maps, nx, ny, wpc);
+    VHP_HIP(hipGetLastError());
+  }
+  const std::vector<double> recip = recip_table(nx, ny);
+  VHP_HIP(hipMalloc(&ctx->d_maps_recip, recip.size() * sizeof(double)));
+  VHP_HIP(hipMemcpyAsync(ctx->d_maps_recip, recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->maps_n = n_maps;
+  ctx->maps_nx = nx;
+  ctx->maps_ny = ny;
+  ctx->maps_wpr = wpr;
+  ctx->maps_wpc = wpc;
   return VHP_OK;
 }
 
@@ -474,7 +588,8 @@ int vhp_destroy(vhp_ctx* ctx) {
   DeviceGuard guard(ctx->device);
   hipStreamSynchronize(ctx->stream);
   free_map(ctx);
-  for (void* p : {(void*)ctx->d_src, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
+  free_maps(ctx);
+  for (void* p : {(void*)ctx->d_src, (void*)ctx->d_map_idx, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
     if (p) (void)hipFree(p);
   for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto& pr : ctx->event_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -573,6 +688,63 @@ int vhp_sweep_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int variant,
   const int rc = stage_batch(ctx, "vhp_sweep_batch", src_xy, n_src, dtype == VHP_F64 ? 8 : 4, out_host,
                              [&](int n) { return vhp_sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out); });
   return rc == VHP_OK && n_src > 0 ? vhp_sync(ctx) : rc;
+}
+
+static int set_maps_common(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, bool from_device) {
+  const std::string who = from_device ? "vhp_set_maps_device" : "vhp_set_maps";
+  if (!ctx || !src || n_maps < 1 || nx <= 0 || ny <= 0) return fail(ctx, VHP_ERR_ARG, who + ": bad argument");
+  if (nx > VHP_MAX_SIDE || ny > VHP_MAX_SIDE) return fail(ctx, VHP_ERR_TOO_LARGE, who + ": grid side exceeds VHP_MAX_SIDE");
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  free_maps(ctx);  // ("field_stride" stays: vhp_set_map owns its reset)
+  const int rc = build_maps(ctx, src, n_maps, nx, ny, from_device);
+  if (rc != VHP_OK) free_maps(ctx);  // (an empty stack, not a half-built one)
+  return rc;
+}
+
+int vhp_set_maps(vhp_ctx* ctx, const uint8_t* occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, occ, n_maps, nx, ny, false); }
+int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, d_occ, n_maps, nx, ny, true); }
+
+int vhp_sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out) {
+  if (!ctx || !d_src_xy || !d_map_idx || !d_out || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: bad argument");
+  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch_device: no maps set");
+  if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
+  if (reinterpret_cast<uintptr_t>(d_out) % (dtype == VHP_F64 ? 8 : 4) != 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: d_out is not aligned to its element type");
+  if (ctx->opt_field_stride > 0 && ctx->opt_field_stride < (long long)ctx->maps_nx * ctx->maps_ny)
+    return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: field_stride is smaller than a field (nx * ny elements): the fields would overlap");
+  if (n_src == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  const hipError_t e = dtype == VHP_F64 ? launch_maps_sweep<double>(ctx, d_src_xy, d_map_idx, n_src, static_cast<double*>(d_out))
+                                        : launch_maps_sweep<float>(ctx, d_src_xy, d_map_idx, n_src, static_cast<float*>(d_out));
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("maps sweep launch: ") + hipGetErrorString(e));
+  VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  return VHP_OK;
+}
+
+int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host) {
+  if (!ctx || !src_xy || !map_idx || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch: bad argument");
+  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch: no maps set");
+  if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
+  struct PackedHere { long long& v; long long keep; ~PackedHere() { v = keep; } } packed{ctx->opt_field_stride, ctx->opt_field_stride};
+  ctx->opt_field_stride = 0;
+  const size_t field = (size_t)ctx->maps_nx * ctx->maps_ny * (dtype == VHP_F64 ? 8 : 4);
+  int rc = stage_slices(ctx, "vhp_sweep_maps_batch", src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
+    const hipError_t e = grow(&ctx->d_map_idx, &ctx->d_map_idx_cap, (size_t)n * sizeof(int32_t), false, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_sweep_maps_batch: scratch: ") + hipGetErrorString(e));
+    VHP_HIP(hipMemcpyAsync(ctx->d_map_idx, map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return vhp_sweep_maps_batch_device(ctx, ctx->d_src, ctx->d_map_idx, n, dtype, ctx->d_out);
+  });
+  if (rc != VHP_OK || n_src == 0) return rc;
+  rc = vhp_sync(ctx);
+  // the sweep leaves a rejected source's field unwritten: zero here, not what the scratch held
+  for (int i = 0; i < n_src; ++i) {
+    const int x = src_xy[2 * i], y = src_xy[2 * i + 1], k = map_idx[i];
+    if (x < 0 || y < 0 || x >= ctx->maps_nx || y >= ctx->maps_ny || k < 0 || k >= ctx->maps_n)
+      std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
+  }
+  return rc;
 }
 
 int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {

@@ -161,6 +161,14 @@ struct UnitGeom {
            // segment starts on a 128-byte line of the output (partial 64-byte sectors cost a read-modify-write)
 };
 
+// A stack of maps of one size (vhp_set_maps): the map of source s is idx[s] (0 .. n-1); map k's packed copies are
+// those of map 0 moved by k*rows_stride and k*cols_stride words.
+struct MapStack {
+  const int32_t* idx;
+  int n;
+  long long rows_stride, cols_stride;
+};
+
 // Slide of the y-major column grid for a quadrant (0 .. 15), 0 if the slid grid would need one strip more
 // than `max_strips`.
 template <int DX>
@@ -1126,10 +1134,11 @@ __device__ __forceinline__ SubGroup whole_workgroup() {
 // CU; the R = 2 multi-round shape runs 8-wavefront workgroups, three per CU.
 // One workgroup slot: slot b sweeps unit b, or (descriptors from vhp_order_units) `count` units
 // order[first .. first+count) side by side, each with 1/G of the wavefronts.
-template <int R, bool MULTI, typename OutT>
+// MAPS (vhp_sweep_fronts_maps): every source sweeps a map of its own from a stack of maps of one size (`stack`).
+template <int R, bool MULTI, typename OutT, bool MAPS = false>
 __device__ __forceinline__ void sweep_slot(const DevMap& m, const int32_t* __restrict__ src_xy, OutT* __restrict__ out, long long field_stride,
                                            int* __restrict__ err_flag, const int* __restrict__ order, const int4* __restrict__ wg_desc,
-                                           int b, double* lds) {
+                                           int b, double* lds, const MapStack stack = {}) {
   int first = b, count = 1, G = 1;
   if (wg_desc) {
     const int4 d = wg_desc[b];
@@ -1157,7 +1166,7 @@ __device__ __forceinline__ void sweep_slot(const DevMap& m, const int32_t* __res
     }
   }
   bool live = sub < count;
-  int s = 0, q = 0, sx = 0, sy = 0;
+  int s = 0, q = 0, sx = 0, sy = 0, k = 0;
   if (live) {
     const int unit = order ? order[first + sub] : first;
     s = unit / kUnitsPerSource;
@@ -1168,6 +1177,16 @@ __device__ __forceinline__ void sweep_slot(const DevMap& m, const int32_t* __res
       if (sg.tid == 0 && q == 0) atomicOr(err_flag, 1);
       live = false;
     }
+    if constexpr (MAPS) {
+      // one scalar load per subgroup, before the sweep: the map of source s, rejected like a source outside the grid
+      if (live) {
+        k = stack.idx[s];
+        if (k < 0 || k >= stack.n) {
+          if (sg.tid == 0 && q == 0) atomicOr(err_flag, 1);
+          live = false;
+        }
+      }
+    }
   }
   if (!live) {  // vacant subgroup or rejected source: only attend the partners' barriers
     for (int t = 0; t <= sg.tmax_floor; ++t) __syncthreads();
@@ -1177,7 +1196,17 @@ __device__ __forceinline__ void sweep_slot(const DevMap& m, const int32_t* __res
 #define VHP_FRONT_NT false
 #endif
   StoreEmit<OutT, MULTI, VHP_FRONT_NT> emit(out + (size_t)s * field_stride, m.nx, m.ny);
-  sweep_quadrant<R>(m, emit, sx, sy, q, lds + (size_t)sub * sweep_lds_doubles(R, sg.W, MULTI), sg);
+  if constexpr (MAPS) {
+    // (each subgroup its own map: a packed workgroup may hold units of different maps.  k is uniform; said so, the pointers
+    // stay in SGPRs -- else the phi above leaves k in a VGPR and both pointers are spilled)
+    const long long ku = __builtin_amdgcn_readfirstlane(k);
+    DevMap mk = m;
+    mk.rows += ku * stack.rows_stride;
+    mk.cols += ku * stack.cols_stride;
+    sweep_quadrant<R>(mk, emit, sx, sy, q, lds + (size_t)sub * sweep_lds_doubles(R, sg.W, MULTI), sg);
+  } else {
+    sweep_quadrant<R>(m, emit, sx, sy, q, lds + (size_t)sub * sweep_lds_doubles(R, sg.W, MULTI), sg);
+  }
 }
 
 // grid = slots: workgroup b sweeps slot b; slots are handed out longest first, which with in-order dispatch is LPT
@@ -1191,6 +1220,17 @@ vhp_sweep_fronts(DevMap m, const int32_t* __restrict__ src_xy, OutT* __restrict_
                  int* __restrict__ err_flag, const int* __restrict__ order, const int4* __restrict__ wg_desc) {
   extern __shared__ double lds[];
   sweep_slot<R, MULTI, OutT>(m, src_xy, out, field_stride, err_flag, order, wg_desc, (int)blockIdx.x, lds);
+}
+
+// The front sweep over a stack of maps (vhp_sweep_maps_batch): as vhp_sweep_fronts, but source s sweeps map stack.idx[s], whose
+// packed copies sit at m.rows + idx*stack.rows_stride and m.cols + idx*stack.cols_stride (m: map 0).  Units, order and barrier
+// counts depend on the grid size and the sources alone, so vhp_order_units and unit_tmax serve it unchanged.
+template <int R, bool MULTI, typename OutT>
+__global__ void __launch_bounds__((R == 2 && MULTI) ? 512 : 1024, R >= 4 ? 4 : ((MULTI && R == 2) ? 6 : 8))
+vhp_sweep_fronts_maps(DevMap m, const int32_t* __restrict__ src_xy, MapStack stack, OutT* __restrict__ out, long long field_stride,
+                      int* __restrict__ err_flag, const int* __restrict__ order, const int4* __restrict__ wg_desc) {
+  extern __shared__ double lds[];
+  sweep_slot<R, MULTI, OutT, true>(m, src_xy, out, field_stride, err_flag, order, wg_desc, (int)blockIdx.x, lds, stack);
 }
 
 // ---------------------------------------------------------------------------
@@ -1307,6 +1347,36 @@ __global__ void vhp_pack_cols(const uint8_t* __restrict__ occ, uint64_t* __restr
   const bool f = y < ny && occ[(size_t)y * nx + x] != 0;
   const uint64_t b = __ballot(f);
   if (lane == 0) cols[(size_t)x * wpc + 1 + w] = b;
+}
+
+// The same for a stack of n_maps maps of nx x ny (map k at occ + k*nx*ny, its words at rows + k*ny*wpr / cols + k*nx*wpc):
+// one launch per copy, blockIdx.y picks the map (stepping by gridDim.y past 65535 maps).
+__global__ void vhp_pack_rows_stack(const uint8_t* __restrict__ occ, uint64_t* __restrict__ rows, int n_maps, int nx, int ny, int wpr) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int words = wpr - 2;
+  if (wave >= words * ny) return;
+  const int y = wave / words, w = wave - y * words;
+  const int x = w * 64 + lane;
+  for (int k = blockIdx.y; k < n_maps; k += gridDim.y) {
+    const bool f = x < nx && occ[(size_t)k * nx * ny + (size_t)y * nx + x] != 0;
+    const uint64_t b = __ballot(f);
+    if (lane == 0) rows[(size_t)k * ny * wpr + (size_t)y * wpr + 1 + w] = b;
+  }
+}
+
+__global__ void vhp_pack_cols_stack(const uint8_t* __restrict__ occ, uint64_t* __restrict__ cols, int n_maps, int nx, int ny, int wpc) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int words = wpc - 2;
+  if (wave >= words * nx) return;
+  const int x = wave / words, w = wave - x * words;
+  const int y = w * 64 + lane;
+  for (int k = blockIdx.y; k < n_maps; k += gridDim.y) {
+    const bool f = y < ny && occ[(size_t)k * nx * ny + (size_t)y * nx + x] != 0;
+    const uint64_t b = __ballot(f);
+    if (lane == 0) cols[(size_t)k * nx * wpc + (size_t)x * wpc + 1 + w] = b;
+  }
 }
 
 }  // namespace vhp
