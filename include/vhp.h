@@ -178,6 +178,28 @@ int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* 
                               int32_t* pivots_xy);
 int vhp_planner_batch_group(const vhp_ctx* ctx);
 
+/* Many planner queries across a stack of maps in one call: query q runs on map map_idx[q] of the stack of vhp_set_maps and gives
+ * exactly what vhp_set_map(that map) + vhp_planner_solve gives for it alone (status, pivots, labels, union, last local field -- bit
+ * for bit).  Semantics as vhp_planner_solve_batch's, with these differences.  The four validation codes of status[q] are checked
+ * against the query's own map.  The call fails with VHP_ERR_ARG also for a null map_idx and for any map_idx[q] outside
+ * 0..n_maps-1 (checked on the host before anything runs), and with VHP_ERR_NO_MAP when no stack is set.  G follows
+ * vhp_planner_solve_batch's rule on the stack's nx x ny, with the context's options ("planner_batch_group" caps it; "kernel" = 1
+ * runs every query on the front sweep, G = 1); the sweep launch reads each query's map index on the device (vhp_lat_maps_sweep).
+ * The first such call after a vhp_set_maps that takes the latency sweep builds the stack's diagonal maps (the latency sweep's copy
+ * of every map, DiagMaps::words(nx, ny) words a map), kept until the next vhp_set_maps or vhp_destroy.  The results have state of
+ * their own: they stay until the next maps-batch solve or vhp_set_maps; vhp_set_map leaves them alone, and this call leaves the
+ * single map, the plain planner's results and vhp_planner_solve_batch's results and group alone.  vhp_last_elapsed_ms times the
+ * whole call; vhp_last_sweep_kernel reports 4 or 1.  vhp_planner_maps_batch_results_device / vhp_planner_maps_batch_results /
+ * vhp_planner_maps_batch_group are vhp_planner_batch_results_device / vhp_planner_batch_results / vhp_planner_batch_group for
+ * the last maps batch (VHP_ERR_ARG before any since the last vhp_set_maps). */
+int vhp_planner_solve_maps_batch(vhp_ctx* ctx, const int32_t* queries, const int32_t* map_idx, const double* thresholds,
+                                 int n_queries, uint64_t max_iter, int32_t* status, uint32_t* n_pivots);
+int vhp_planner_maps_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global,
+                                          const double** vis_local, const int32_t** pivots_xy);
+int vhp_planner_maps_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local,
+                                   int32_t* pivots_xy);
+int vhp_planner_maps_batch_group(const vhp_ctx* ctx);
+
 /* Replaces reconstructPath() (solver.cpp:1183-1213): walks came_from -> pivots from
  * `end` until the label repeats; writes the path start-first into path_xy (capacity
  * cap points), its point count into *n_path, the summed eval_d length into *length.
@@ -251,7 +273,7 @@ int vhp_timing_collect(vhp_ctx* ctx, float* ms_out, int cap, int* n);
 int vhp_set_option(vhp_ctx* ctx, const char* key, long long value);
 /* Which kernel the last batch sweep of this context launched: 1 = front sweep (vhp_sweep_fronts),
  * 3 = pool sweep (vhp_pool_sweep), 4 = latency sweep
- * (vhp_lat_sweep), 0 = none yet.  For benchmarks and profiles. */
+ * (vhp_lat_sweep; vhp_lat_maps_sweep on a stack of maps), 0 = none yet.  For benchmarks and profiles. */
 int vhp_last_sweep_kernel(const vhp_ctx* ctx);
 
 /* The max-union of a batch of fields and the source that attains it, on the device: best[c] = max over k of field k at cell c,

@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "vhp_union_fields_device", "vhp_union_partials_device", "vhp_multi_union_fields",
     "vhp_planner_solve_batch", "vhp_planner_batch_results_device", "vhp_planner_batch_results", "vhp_planner_batch_group",
     "vhp_set_maps", "vhp_set_maps_device", "vhp_sweep_maps_batch", "vhp_sweep_maps_batch_device",
+    "vhp_planner_solve_maps_batch", "vhp_planner_maps_batch_results_device", "vhp_planner_maps_batch_results", "vhp_planner_maps_batch_group",
 )
 
 
@@ -100,6 +101,10 @@ def load_library():
     lib.vhp_planner_batch_results_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.vhp_planner_batch_results.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.vhp_planner_batch_group.argtypes = [vp]
+    lib.vhp_planner_solve_maps_batch.argtypes = [vp, vp, vp, vp, i32, u64, vp, vp]
+    lib.vhp_planner_maps_batch_results_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.vhp_planner_maps_batch_results.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.vhp_planner_maps_batch_group.argtypes = [vp]
     lib.vhp_sweep_batch_variant.argtypes = [vp, vp, i32, f64, f64, vp]
     lib.vhp_planner_solve_variant.argtypes = [vp, i32, i32, i32, i32, f64, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_sweep_batch_offset.argtypes = [vp, vp, i32, f64, vp]
@@ -336,6 +341,10 @@ class Context:
         st = np.zeros(n, np.int32)
         npiv = np.zeros(n, np.uint32)
         self._check(self.lib.vhp_planner_solve_batch(self.h, _ptr(q), _ptr(thr), n, int(max_iter), _ptr(st), _ptr(npiv)))
+        return self._batch_outputs(st, npiv, outputs, self.nx, self.ny, self.lib.vhp_planner_batch_results)
+
+    def _batch_outputs(self, st, npiv, outputs, nx, ny, results):
+        n = len(st)
         out = []
         for k in range(n):
             r = dict(status=int(st[k]), n_pivots=int(npiv[k]))
@@ -344,10 +353,10 @@ class Context:
                 piv = np.zeros((r["n_pivots"] + 1, 2), np.int32)
                 came = vg = vl = None
                 if solved:
-                    came = np.empty((self.ny, self.nx), np.uint64)
-                    vg = np.empty((self.ny, self.nx), np.float64)
-                    vl = np.empty((self.ny, self.nx), np.float64)
-                    self._check(self.lib.vhp_planner_batch_results(self.h, k, _ptr(came), _ptr(vg), _ptr(vl), _ptr(piv)))
+                    came = np.empty((ny, nx), np.uint64)
+                    vg = np.empty((ny, nx), np.float64)
+                    vl = np.empty((ny, nx), np.float64)
+                    self._check(results(self.h, k, _ptr(came), _ptr(vg), _ptr(vl), _ptr(piv)))
                 r.update(came_from=came, vis_global=vg, vis_local=vl, pivots=piv)
             out.append(r)
         return out
@@ -362,6 +371,30 @@ class Context:
     def planner_batch_group(self):
         """Queries per group of the last planner_solve_batch (0: none yet)."""
         return int(self.lib.vhp_planner_batch_group(self.h))
+
+    def planner_solve_maps_batch(self, queries, map_index, thresholds, max_iter, outputs=True):
+        """vhp_planner_solve_maps_batch: planner_solve_batch across the stack of set_maps -- query q on map map_index[q].  Returns
+        planner_solve_batch's list of dicts (fields [maps_ny, maps_nx])."""
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1, 4)
+        idx = np.ascontiguousarray(map_index, np.int32).reshape(-1)
+        if len(idx) != len(q):
+            raise ValueError("planner_solve_maps_batch: %d queries but %d map indices" % (len(q), len(idx)))
+        n = len(q)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float64), (n,)))
+        st = np.zeros(n, np.int32)
+        npiv = np.zeros(n, np.uint32)
+        self._check(self.lib.vhp_planner_solve_maps_batch(self.h, _ptr(q), _ptr(idx), _ptr(thr), n, int(max_iter), _ptr(st), _ptr(npiv)))
+        return self._batch_outputs(st, npiv, outputs, self.maps_nx, self.maps_ny, self.lib.vhp_planner_maps_batch_results)
+
+    def planner_maps_batch_results_device(self, q):
+        """Raw device pointers of query q of the last planner_solve_maps_batch (the layout of planner_batch_results_device)."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._check(self.lib.vhp_planner_maps_batch_results_device(self.h, int(q), *[C.byref(v) for v in p]))
+        return dict(labels=p[0].value, vis_global=p[1].value, vis_local=p[2].value, pivots=p[3].value)
+
+    def planner_maps_batch_group(self):
+        """Queries per group of the last planner_solve_maps_batch (0: none yet)."""
+        return int(self.lib.vhp_planner_maps_batch_group(self.h))
 
     def sweep_batch_variant(self, sources, alpha=1.0, fac=1.0):
         """MATLAB-flavoured sweep (getAccessibilityMap.m): fields [n, ny, nx] float64."""

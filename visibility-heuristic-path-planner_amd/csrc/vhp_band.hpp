@@ -81,6 +81,30 @@ struct DiagMaps {
   }
 };
 
+// Word k (0 .. words(nx, ny)) of a map's DiagMaps, read from its ROW-packed copy (Map::rows, wpr words a row): the pad words at either
+// end of a run are 0.  What vhp_pack_diag computes from the byte map, for the stacks of vhp_set_maps, which keep no byte maps
+// (vhp_lat.hip vhp_pack_diag_stack; the CPU simulator builds its stacks' diagonal maps with it too).
+VHP_HD uint64_t diag_word_from_rows(const uint64_t* rows, int wpr, int nx, int ny, size_t k) {
+  const size_t by_y0 = DiagMaps::offset(nx, ny, 2);
+  const bool by_y = k >= by_y0;
+  const int wpd = by_y ? DiagMaps::wpdy(ny) : DiagMaps::wpdx(nx);
+  const size_t r = by_y ? k - by_y0 : k;
+  const size_t run_all = r / (size_t)wpd;
+  const int word = (int)(r - run_all * (size_t)wpd), n_runs = DiagMaps::runs(nx, ny);
+  const bool anti = run_all >= (size_t)n_runs;
+  const int id = (int)(anti ? run_all - (size_t)n_runs : run_all);
+  if (word == 0 || word == wpd - 1) return 0;
+  uint64_t bits = 0;
+  for (int t = 0; t < 64; ++t) {
+    const int c = (word - 1) * 64 + t;  // x (by x) or y (by y)
+    // main: y - x = id - (nx - 1); anti: y + x = id
+    const int x = by_y ? (anti ? id - c : c - (id - (nx - 1))) : c;
+    const int y = by_y ? c : (anti ? id - c : c + (id - (nx - 1)));
+    if (x >= 0 && x < nx && y >= 0 && y < ny && ((rows[(size_t)y * wpr + 1 + (x >> 6)] >> (x & 63)) & 1ull)) bits |= 1ull << t;
+  }
+  return bits;
+}
+
 // a sweeper's words for its storer (in the sweeper's dummy slots)
 VHP_FN int* post_of(const Shared& sh, int w) { return reinterpret_cast<int*>(sh.lds + sh.L.dummies + w * kLatDummy); }
 
@@ -948,11 +972,13 @@ struct BandYStore {
 
 // One wavefront of a unit's workgroup: sweeper w (w < W) or the storer of sweeper w - W.
 // MULTI: the build for launches with more than one workgroup per unit (LatArgs::halves > 1); the build for one holds none of that code
-template <typename OutT, bool ODD = false, bool MULTI = false>
+// STACK: the build for a stack of maps (vhp_lat_maps_sweep): run() moves the worker's maps to the source's map (stk, set after init)
+template <typename OutT, bool ODD = false, bool MULTI = false, bool STACK = false>
 struct BandWorker {
   static constexpr int kRoles = 2;  // wavefronts per sweeper (the simulator and the launcher size the workgroup by it)
   static constexpr int kTilePitch = kBandTStrideDown;  // ... and the LDS layout's tiles by this
   LatArgs<OutT> a;
+  LatMapStack stk;   // (STACK only)
   Shared sh;
   int w, W;
   int H, half;   // workgroups per unit, and which of them this is (run)
@@ -1098,6 +1124,10 @@ struct BandWorker {
     // (the planners' control words together, before any of them is looked at: one trip to memory, then the source's)
     int sx, sy;
     const int slot0 = a.slot_base ? *a.slot_base : 0;
+    // (the source's map: one wave-uniform load beside the source's, the index a scalar from here on -- in a vector register it would
+    // take the map pointers with it, out of the scalar registers)
+    int k_map = 0;
+    if constexpr (STACK) k_map = uniform(stk.map_idx[uniform(slot0) + s]);
     if (a.pivot_rec) {  // the planner's loop: {done, nb, x, y} in one load
       int done, nb;
       g_load_rec4(a.pivot_rec, 0, done, nb, sx, sy);
@@ -1110,9 +1140,14 @@ struct BandWorker {
       sy = uniform(a.src_xy[2 * si + 1]);
     }
     if (a.slot_base && sx < 0) return;
-    if (sx < 0 || sy < 0 || sx >= a.m.nx || sy >= a.m.ny) {  // units of a rejected source do nothing
+    if (sx < 0 || sy < 0 || sx >= a.m.nx || sy >= a.m.ny || (STACK && (k_map < 0 || k_map >= stk.n_maps))) {  // units of a rejected source (or map) do nothing
       if (qo == 0 && w == 0 && half == 0) g_store_scalar_if(lane == 0, a.err_flag, vi(0), 1);
       return;
+    }
+    if constexpr (STACK) {  // this worker's copies of the maps, moved to map k_map (every map has the launch's size: nothing else changes)
+      a.m.rows += (long long)k_map * stk.rows_stride;
+      a.m.cols += (long long)k_map * stk.cols_stride;
+      a.dmap += (long long)k_map * stk.diag_stride;
     }
     OutT* field = a.out + (size_t)(s + uniform(slot0)) * a.field_stride;
     if (w < W) {

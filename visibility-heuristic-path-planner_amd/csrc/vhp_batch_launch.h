@@ -46,6 +46,10 @@ struct BatchArgs {
   const int* d_run_if = nullptr;
   bool lat_dead_cells_are_zero = false;  // ... and dead strips store nothing: the field holds +0.0 wherever the launch does not write
   unsigned long long pool_epoch = 0;  // pool sweep: the tag of this launch's boundary-line entries: never 0, never reused on this scratch
+  // latency sweep, fp64: a stack of n_maps maps of this size (vhp_set_maps), rows / cols / dmap those of map 0; field s is swept on map
+  // d_map_idx[*d_slot_base + s] (vhp_lat.hip vhp_lat_maps_sweep) -- or null: one map
+  const int32_t* d_map_idx = nullptr;
+  int n_maps = 0;
 };
 
 // The pool sweep (vhp_pool.hip): d_queue is scratch of pool_scratch_bytes (pull counter, unit order, the
@@ -69,5 +73,8 @@ size_t lat_order_bytes();
 // built once per map from the byte map: lat_diag_map_bytes of device memory, zero-filled and packed by lat_pack_diag_maps.
 size_t lat_diag_map_bytes(int nx, int ny);
 hipError_t lat_pack_diag_maps(const uint8_t* d_occ, int nx, int ny, uint64_t* d_dmap, hipStream_t stream);
+// ... and for a stack of n_maps maps from their row-packed words (map k's at d_rows + k * ny * wpr): map k's diagonal maps at
+// d_dmap + k * lat_diag_map_bytes(nx, ny) / 8, every word written
+hipError_t lat_pack_diag_stack(const uint64_t* d_rows, int n_maps, int nx, int ny, int wpr, uint64_t* d_dmap, hipStream_t stream);
 
 }  // namespace vhp

@@ -106,6 +106,9 @@ struct vhp_ctx {
   double* d_maps_recip = nullptr;   // one reciprocal table for max(maps_nx, maps_ny)
   int32_t* d_map_idx = nullptr;     // host-buffer form's slice of map indices (grow)
   size_t d_map_idx_cap = 0;
+  uint64_t* d_maps_dmap = nullptr;  // every map's diagonal maps (map k's k * lat_diag_map_bytes further): built by the first planner batch
+                                    // on the stack that takes the latency sweep (vhp_planner_solve_maps_batch), kept until the stack goes
+  vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
 };
 
 namespace {
@@ -207,9 +210,10 @@ void free_map(vhp_ctx* c) {
 }
 
 void free_maps(vhp_ctx* c) {
-  for (void* p : {(void*)c->d_maps_rows, (void*)c->d_maps_cols, (void*)c->d_maps_recip})
+  for (void* p : {(void*)c->d_maps_rows, (void*)c->d_maps_cols, (void*)c->d_maps_recip, (void*)c->d_maps_dmap})
     if (p) (void)hipFree(p);
-  c->d_maps_rows = c->d_maps_cols = nullptr;
+  vhp::batch_free(c->maps_batch);
+  c->d_maps_rows = c->d_maps_cols = c->d_maps_dmap = nullptr;
   c->d_maps_recip = nullptr;
   c->maps_n = c->maps_nx = c->maps_ny = c->maps_wpr = c->maps_wpc = 0;
 }
@@ -261,13 +265,16 @@ vhp::SweepPlan plan_for_maps(const vhp_ctx* c, int n_src, bool f64) {
                           {1, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, false, false, false});
 }
 
-// What sweeps a batch of n_src sources on the context's grid with its options (vhp_choice.hpp).
-vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) {
-  const bool lat_ok = vhp::lat_supported(c->nx, c->ny);
-  return vhp::plan_sweep({c->nx, c->ny, n_src, c->n_cus, f64,
+// What sweeps a batch of n_src sources on an nx x ny grid with the context's options (vhp_choice.hpp).
+vhp::SweepPlan plan_for_grid(const vhp_ctx* c, int nx, int ny, int n_src, bool f64) {
+  const bool lat_ok = vhp::lat_supported(nx, ny);
+  return vhp::plan_sweep({nx, ny, n_src, c->n_cus, f64,
                           {c->opt_kernel, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, lat_ok,
-                          vhp::pool_supported(c->nx, c->ny), lat_ok && vhp::lat_scratch_bytes(n_src, c->nx, c->ny) <= ((size_t)2 << 30)});
+                          vhp::pool_supported(nx, ny), lat_ok && vhp::lat_scratch_bytes(n_src, nx, ny) <= ((size_t)2 << 30)});
 }
+
+// ... on the context's grid
+vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) { return plan_for_grid(c, c->nx, c->ny, n_src, f64); }
 
 // The planner's sweeps of n_src sources: the plan, and the front sweep's shape and round scratch (n_workgroups) from it.
 hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workgroups, vhp::SweepPlan* plan) {
@@ -330,18 +337,28 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
   return el;
 }
 
-// The pool sweep (lat = false) or the latency sweep (lat = true), through vhp_batch_launch.h.
+// The pool sweep (lat = false) or the latency sweep (lat = true), through vhp_batch_launch.h.  With d_map_idx: the latency sweep on the
+// stack of maps, source s on map d_map_idx[s] (its diagonal maps built: d_maps_dmap).
 template <typename OutT>
-hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, bool lat) {
+hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, bool lat, const int32_t* d_map_idx = nullptr) {
+  const bool on_stack = d_map_idx != nullptr;
+  const int nx = on_stack ? c->maps_nx : c->nx, ny = on_stack ? c->maps_ny : c->ny;
   // (the scratch is an allocation of its own: nothing but these two kernels may write the tagged lines)
-  const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, c->nx, c->ny) : vhp::pool_scratch_bytes(n_src, c->nx, c->ny);
+  const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, nx, ny) : vhp::pool_scratch_bytes(n_src, nx, ny);
   if (hipError_t eo = grow(&c->d_pool, &c->d_pool_cap, scratch, true, c->stream); eo != hipSuccess) return eo;
   vhp::BatchArgs a;
-  a.rows = c->d_rows; a.cols = c->d_cols; a.recip = c->d_recip; a.dmap = c->d_dmap;
-  a.wpr = c->wpr; a.wpc = c->wpc; a.nx = c->nx; a.ny = c->ny;
+  if (on_stack) {
+    a.rows = c->d_maps_rows; a.cols = c->d_maps_cols; a.recip = c->d_maps_recip; a.dmap = c->d_maps_dmap;
+    a.wpr = c->maps_wpr; a.wpc = c->maps_wpc; a.nx = nx; a.ny = ny;
+    a.d_map_idx = d_map_idx;
+    a.n_maps = c->maps_n;
+  } else {
+    a.rows = c->d_rows; a.cols = c->d_cols; a.recip = c->d_recip; a.dmap = c->d_dmap;
+    a.wpr = c->wpr; a.wpc = c->wpc; a.nx = c->nx; a.ny = c->ny;
+  }
   a.d_src = d_src; a.n_src = n_src; a.d_out = d_out;
   a.dtype = sizeof(OutT) == 8 ? VHP_F64 : VHP_F32;
-  a.field_stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)c->nx * c->ny;
+  a.field_stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)nx * ny;
   a.d_err = c->d_err;
   a.d_queue = c->d_pool;
   a.pool_epoch = ++c->pool_epoch;
@@ -521,14 +538,15 @@ int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, boo
 // G of a batch solve (vhp_planner_solve_batch): the largest of 32, 16, 8, 4, 2 for which a launch of G sources takes the latency sweep
 // and G queries' state fits in a quarter of the free device memory, else 1 -- capped by "planner_batch_group" --; 0 where even one
 // source does not take the latency sweep (the queries then run one by one on the front sweep).
-int planner_batch_group_size(const vhp_ctx* c, uint64_t max_iter) {
-  if (plan_for(c, 1, true).kernel != 4) return 0;
+// (On the stack of maps: the same rule on the stack's nx x ny.)
+int planner_batch_group_size(const vhp_ctx* c, int nx, int ny, uint64_t max_iter) {
+  if (plan_for_grid(c, nx, ny, 1, true).kernel != 4) return 0;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-  const size_t per_query = vhp::kBatchBytesPerCell * (size_t)c->nx * c->ny + 2 * (size_t)(max_iter + 2) * sizeof(int32_t);
+  const size_t per_query = vhp::kBatchBytesPerCell * (size_t)nx * ny + 2 * (size_t)(max_iter + 2) * sizeof(int32_t);
   int g = 1;
   for (int G = vhp::kBatchMaxGroup; G > 1; G /= 2)
-    if (plan_for(c, G, true).kernel == 4 && (size_t)G * per_query <= free_b / 4) { g = G; break; }
+    if (plan_for_grid(c, nx, ny, G, true).kernel == 4 && (size_t)G * per_query <= free_b / 4) { g = G; break; }
   return c->opt_planner_batch_group > 0 ? std::min(g, c->opt_planner_batch_group) : g;
 }
 
@@ -543,10 +561,10 @@ hipError_t launch_batch_fronts(vhp_ctx* c, const vhp::DevMap& m, const vhp::Plan
   return hipGetLastError();
 }
 
-// The last batch's slot of query q, or an error for the _results entry points.
-int batch_slot(vhp_ctx* ctx, const char* who, int q, int* slot) {
-  const vhp::BatchState& b = ctx->batch;
-  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": no batch solved on this map");
+// The last batch's slot of query q, or an error for the _results entry points (of the maps batch with `maps`).
+int batch_slot(vhp_ctx* ctx, const char* who, int q, int* slot, bool maps = false) {
+  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
   if (q < 0 || q >= (int)b.slot_of.size()) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query index out of range");
   if (b.slot_of[q] < 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query " + std::to_string(q) + " failed validation and has no results");
   *slot = b.slot_of[q];
@@ -1231,11 +1249,11 @@ int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* 
   VHP_ON_DEVICE(ctx);
   vhp::DevMap pm = dev_map(ctx);
   vhp::BatchState& b = ctx->batch;
-  const int G = planner_batch_group_size(ctx, max_iter);
+  const int G = planner_batch_group_size(ctx, ctx->nx, ctx->ny, max_iter);
   b.lat_sweep = nullptr;
   b.front_sweep = nullptr;
   if (G > 0) {
-    b.lat_sweep = [ctx](const int32_t* cand, int n, double* out) {
+    b.lat_sweep = [ctx](const int32_t* cand, const int32_t*, int n, double* out) {
       ctx->lat_slot_base = reinterpret_cast<const int*>(ctx->batch.n_done + 1);   // (a zero: field g of the launch is query g's)
       ctx->lat_dark_unwritten = true;
       const long long stride = ctx->opt_field_stride;
@@ -1254,7 +1272,7 @@ int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* 
     const vhp::SweepPlan plan = plan_for(ctx, 1, true);
     hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
     if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
-    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d) {
+    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int) {
       switch (plan.R) {
         case 1: return plan.multi ? launch_batch_fronts<1, true>(ctx, pm, d, plan.W) : launch_batch_fronts<1, false>(ctx, pm, d, plan.W);
         case 2: return plan.multi ? launch_batch_fronts<2, true>(ctx, pm, d, plan.W) : launch_batch_fronts<2, false>(ctx, pm, d, plan.W);
@@ -1289,6 +1307,95 @@ int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* 
   VHP_ON_DEVICE(ctx);
   std::string msg;
   const int rc = vhp::batch_results_host(ctx->batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
+  if (rc != VHP_OK) ctx->err = msg;
+  return rc;
+}
+
+int vhp_planner_solve_maps_batch(vhp_ctx* ctx, const int32_t* queries, const int32_t* map_idx, const double* thresholds, int n_queries,
+                                 uint64_t max_iter, int32_t* status, uint32_t* n_pivots) {
+  if (!ctx) return VHP_ERR_ARG;
+  if (n_queries < 1 || n_queries > vhp::kBatchMaxQueries) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: n_queries outside 1..64");
+  if (!queries || !map_idx || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: null array");
+  if (max_iter > (1u << 24)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
+  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_maps_batch: no maps set");
+  for (int q = 0; q < n_queries; ++q)
+    if (map_idx[q] < 0 || map_idx[q] >= ctx->maps_n)
+      return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: query " + std::to_string(q) + ": map index outside the stack");
+  VHP_ON_DEVICE(ctx);
+  const int nx = ctx->maps_nx, ny = ctx->maps_ny;
+  vhp::DevMap pm = stack_dev_map(ctx);
+  vhp::BatchState& b = ctx->maps_batch;
+  const int G = planner_batch_group_size(ctx, nx, ny, max_iter);
+  b.lat_sweep = nullptr;
+  b.front_sweep = nullptr;
+  if (G > 0) {
+    if (!ctx->d_maps_dmap) {  // (the stack's diagonal maps: built once, by the first batch that sweeps them)
+      VHP_HIP(hipMalloc(&ctx->d_maps_dmap, vhp::lat_diag_map_bytes(nx, ny) * ctx->maps_n));
+      const hipError_t e = vhp::lat_pack_diag_stack(ctx->d_maps_rows, ctx->maps_n, nx, ny, ctx->maps_wpr, ctx->d_maps_dmap, ctx->stream);
+      if (e != hipSuccess) {
+        (void)hipFree(ctx->d_maps_dmap);
+        ctx->d_maps_dmap = nullptr;
+        return fail(ctx, VHP_ERR_HIP, std::string("vhp_planner_solve_maps_batch: diagonal maps: ") + hipGetErrorString(e));
+      }
+    }
+    b.lat_sweep = [ctx](const int32_t* cand, const int32_t* d_map_idx, int n, double* out) {
+      ctx->lat_slot_base = reinterpret_cast<const int*>(ctx->maps_batch.n_done + 1);   // (a zero: field g of the launch is query g's)
+      ctx->lat_dark_unwritten = true;
+      const long long stride = ctx->opt_field_stride;
+      ctx->opt_field_stride = 0;  // (the queries' local fields are packed)
+      const bool timing = ctx->timing;
+      ctx->timing = false;  // (as in vhp_planner_solve's loop)
+      const hipError_t e = launch_batch_sweep<double>(ctx, cand, n, out, true, d_map_idx);
+      ctx->timing = timing;
+      ctx->opt_field_stride = stride;
+      ctx->lat_slot_base = nullptr;
+      ctx->lat_dark_unwritten = false;
+      return e;
+    };
+    ctx->last_kernel = 4;
+  } else {
+    const vhp::SweepPlan plan = plan_for_grid(ctx, nx, ny, 1, true);
+    hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
+    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int k) {
+      vhp::DevMap mk = pm;  // (map k of the stack: map 0's packed copies moved by k strides)
+      mk.rows += (size_t)k * mk.ny * mk.wpr;
+      mk.cols += (size_t)k * mk.nx * mk.wpc;
+      switch (plan.R) {
+        case 1: return plan.multi ? launch_batch_fronts<1, true>(ctx, mk, d, plan.W) : launch_batch_fronts<1, false>(ctx, mk, d, plan.W);
+        case 2: return plan.multi ? launch_batch_fronts<2, true>(ctx, mk, d, plan.W) : launch_batch_fronts<2, false>(ctx, mk, d, plan.W);
+        default: return plan.multi ? launch_batch_fronts<4, true>(ctx, mk, d, plan.W) : launch_batch_fronts<4, false>(ctx, mk, d, plan.W);
+      }
+    };
+    ctx->last_kernel = 1;
+  }
+  const vhp::BatchStack st{map_idx, ctx->d_maps_rows, (long long)ny * ctx->maps_wpr, ctx->maps_wpr};
+  std::string msg;
+  const int rc = vhp::planner_solve_batch(b, pm, nullptr, nullptr, ctx->stream, ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter,
+                                          G > 0 ? G : 1, status, n_pivots, &msg, &st);
+  ctx->timed = true;
+  if (!msg.empty()) ctx->err = msg;
+  return rc;
+}
+
+int vhp_planner_maps_batch_group(const vhp_ctx* ctx) { return ctx && ctx->maps_batch.solved ? ctx->maps_batch.group : 0; }
+
+int vhp_planner_maps_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
+                                          const int32_t** pivots_xy) {
+  if (!ctx) return VHP_ERR_ARG;
+  int k = 0;
+  if (int rc = batch_slot(ctx, "vhp_planner_maps_batch_results_device", q, &k, true); rc != VHP_OK) return rc;
+  vhp::batch_results_device(ctx->maps_batch, k, labels, vis_global, vis_local, pivots_xy);
+  return VHP_OK;
+}
+
+int vhp_planner_maps_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
+  if (!ctx) return VHP_ERR_ARG;
+  int k = 0;
+  if (int rc = batch_slot(ctx, "vhp_planner_maps_batch_results", q, &k, true); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  std::string msg;
+  const int rc = vhp::batch_results_host(ctx->maps_batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
 }

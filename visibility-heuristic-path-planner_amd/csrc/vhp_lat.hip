@@ -60,6 +60,22 @@ __global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_sweep(LatArgs<OutT> a)
 #endif
 }
 
+// The latency sweep on a stack of maps (fp64, the planner's fields): vhp_lat_sweep's band build with the STACK flag -- every unit reads
+// its source's map index once, before its sweep, and moves its maps there (vhp_band.hpp BandWorker::run).  The stack is an argument of
+// its own: LatArgs, and with it the eight instantiations above, stay as they are.
+template <bool ODD, bool MULTI>
+__global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_maps_sweep(LatArgs<double> a, LatMapStack st) {
+  extern __shared__ double lds[];
+  const Layout L = make_layout(kLatWaves, 1, a.m.nx, a.m.ny, kLatTilePitch);
+  using WorkerT = BandWorker<double, ODD, MULTI, true>;
+  WorkerT::clear(lds, L, (int)threadIdx.x, kLatThreads);
+  __syncthreads();
+  WorkerT wk;
+  wk.init(a, lds, L, uniform((int)(threadIdx.x >> 6)));
+  wk.stk = st;
+  wk.run((int)blockIdx.x);
+}
+
 // A whole planner iteration as ONE launch (the reference's loop body, src/visibilityBasedSolver.cpp:127-141 with updateVisibility()
 // :379-565: sweep, union, labels, heuristic, next pivot): the first eight workgroups are the eight octants of the pivot's sweep, the
 // others run the epilogue (vhp_planner_dev.hip.h) behind them -- the loads that do not depend on the sweep on their way while it runs,
@@ -113,6 +129,16 @@ __global__ void vhp_pack_diag(const uint8_t* __restrict__ occ, uint64_t* __restr
     if (x >= 0 && x < nx && y >= 0 && y < ny && occ[(size_t)y * nx + x]) bits |= 1ull << t;
   }
   dmap[k] = bits;
+}
+
+// The same words for every map of a stack (vhp_set_maps), from its row-packed copy: map blockIdx.y, gridDim.y, ... of n_maps; pad words
+// written as zeros.  Once per stack, on the first planner batch that needs them (vhp_capi.hip).
+__global__ void vhp_pack_diag_stack(const uint64_t* __restrict__ rows, uint64_t* __restrict__ dmap, int n_maps, int nx, int ny, int wpr) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t words = DiagMaps::words(nx, ny);
+  if (k >= words) return;
+  for (int m = (int)blockIdx.y; m < n_maps; m += (int)gridDim.y)
+    dmap[(size_t)m * words + k] = diag_word_from_rows(rows + (size_t)m * ny * wpr, wpr, nx, ny, k);
 }
 
 // The units of a launch (8 per source: quadrant x {x-major, y-major}) by falling length of their march, for launches of more workgroups
@@ -202,10 +228,14 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   auto k = halves > 1 ? (odd ? vhp_lat_sweep<OutT, true, true> : vhp_lat_sweep<OutT, false, true>)
                       : (odd ? vhp_lat_sweep<OutT, true, false> : vhp_lat_sweep<OutT, false, false>);
 #endif
+  // a stack of maps (a.d_map_idx): the fp64 build of the kernel that reads a map per source
+  auto ks = halves > 1 ? (odd ? vhp_lat_maps_sweep<true, true> : vhp_lat_maps_sweep<false, true>)
+                       : (odd ? vhp_lat_maps_sweep<true, false> : vhp_lat_maps_sweep<false, false>);
+  if (a.d_map_idx && (sizeof(OutT) != 8 || pd)) return hipErrorInvalidValue;
   const size_t lds = lat_lds_bytes(a.nx, a.ny);
   if (lds > kLdsLimit || a.pool_epoch == 0) return hipErrorInvalidValue;
   if (a.raise_lds) {
-    hipError_t e = a.raise_lds(reinterpret_cast<const void*>(k), lds);
+    hipError_t e = a.raise_lds(a.d_map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return e;
   }
 #ifdef VHP_EXP_ONE_KERNEL
@@ -265,7 +295,14 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
     hipLaunchKernelGGL(pool::vhp_lat_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, a.d_lat_order);
     g.order = a.d_lat_order;
   }
-  hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g);
+  if (a.d_map_idx) {
+    if constexpr (sizeof(OutT) == 8) {
+      const LatMapStack st{a.d_map_idx, a.n_maps, (long long)a.ny * a.wpr, (long long)a.nx * a.wpc, (long long)DiagMaps::words(a.nx, a.ny)};
+      hipLaunchKernelGGL(ks, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g, st);
+    }
+  } else {
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g);
+  }
   const hipError_t e = hipGetLastError();
   if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);
   return e;
@@ -282,6 +319,13 @@ size_t lat_diag_map_bytes(int nx, int ny) { return pool::DiagMaps::words(nx, ny)
 hipError_t lat_pack_diag_maps(const uint8_t* d_occ, int nx, int ny, uint64_t* d_dmap, hipStream_t stream) {
   const size_t words = pool::DiagMaps::words(nx, ny);
   hipLaunchKernelGGL(pool::vhp_pack_diag, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d_occ, d_dmap, nx, ny);
+  return hipGetLastError();
+}
+
+hipError_t lat_pack_diag_stack(const uint64_t* d_rows, int n_maps, int nx, int ny, int wpr, uint64_t* d_dmap, hipStream_t stream) {
+  const size_t words = pool::DiagMaps::words(nx, ny);
+  const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernel steps through more maps than that)
+  hipLaunchKernelGGL(pool::vhp_pack_diag_stack, dim3((unsigned)((words + 255) / 256), gy), dim3(256), 0, stream, d_rows, d_dmap, n_maps, nx, ny, wpr);
   return hipGetLastError();
 }
 

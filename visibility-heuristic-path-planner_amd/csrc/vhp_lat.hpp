@@ -74,6 +74,15 @@ struct LatArgs {
   const int* order = nullptr;
 };
 
+// The latency sweep on a stack of maps of one size (vhp_lat_maps_sweep; vhp_set_maps): field s of the launch is swept on map
+// map_idx[*slot_base + s] (0 .. n_maps-1), whose packed copies are those of the launch's map (LatArgs::m, dmap) moved by k times the
+// strides, in words.  A kernel argument of its own, beside LatArgs, so that the one-map instantiations do not carry it.
+struct LatMapStack {
+  const int32_t* map_idx;
+  int n_maps;
+  long long rows_stride, cols_stride, diag_stride;   // ny * wpr, nx * wpc, DiagMaps::words(nx, ny)
+};
+
 #if defined(VHP_DIAG_WINPROF) && !defined(VHP_SIM)  // diagnostic builds only: cycle accounts inside the x-major windows (they cost a few hundred cycles per window themselves)
 #define VHP_WP_T0(var) const unsigned long long var = __builtin_readcyclecounter()
 #define VHP_WP_ADDP(pp, slot, var) { (pp)[slot] += __builtin_readcyclecounter() - var; }

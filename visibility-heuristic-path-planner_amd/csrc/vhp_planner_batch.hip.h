@@ -17,6 +17,9 @@
 // The host enqueues 8 iterations per poll of the done word; the batch runs as groups of at most G queries, one after the other
 // (planner_batch_group_size in vhp_capi.hip).  Where even one source does not take the latency sweep, the groups are single queries and
 // their sweep is the planner's front sweep (vhp_planner_sweep), one local field.
+// The same loop serves a stack of maps (vhp_planner_solve_maps_batch, BatchStack): every slot also has its map index, uploaded with the
+// queries; the group's sweep launch reads the group's slice of them (vhp_lat.hip vhp_lat_maps_sweep), the front sweep is launched on the
+// query's own map.  The epilogue never reads the occupancy, and scale_ depends on nx, ny only: it serves both as it is.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,6 +126,26 @@ __global__ void __launch_bounds__(kEpilogueThreads) vhp_planner_batch_epilogue(i
   if (r.x) atomicAdd(b.n_done, 1u);
 }
 
+// Validation on a stack of maps: the occupancy bit of point i = (x, y, map k) of pts, from the map's row-packed words, into occ[i] --
+// the 2Q cells of a batch in one launch and one copy.
+__global__ void vhp_planner_batch_occupancy(const int4* __restrict__ pts, int n, const uint64_t* __restrict__ rows, long long rows_stride,
+                                            int wpr, uint8_t* __restrict__ occ) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int4 p = pts[i];
+  const uint64_t w = rows[(long long)p.z * rows_stride + (long long)p.y * wpr + 1 + (p.x >> 6)];
+  occ[i] = (uint8_t)((w >> (p.x & 63)) & 1ull);
+}
+
+// A batch on a stack of maps of one size (vhp_set_maps): query q runs on map map_idx[q] (host, checked by the caller); map k's row-packed
+// words are those of map 0 (rows) moved by k * rows_stride.
+struct BatchStack {
+  const int32_t* map_idx;
+  const uint64_t* rows;
+  long long rows_stride;
+  int wpr;
+};
+
 // The device state of a batch: every array holds one slot per query that passed validation (results stay until the next batch or
 // vhp_set_map), plus the host's view of the last batch.
 struct BatchState {
@@ -136,6 +159,8 @@ struct BatchState {
   unsigned int* ticket = nullptr;
   BatchQuery* query = nullptr;
   int32_t* cand = nullptr;
+  int32_t* map_idx = nullptr;            // per slot: its query's map (a batch on a stack of maps)
+  int4* probe = nullptr;                 // a batch on a stack: the 2 * kBatchMaxQueries cells of its validation, then their bits (bytes)
   unsigned int* n_done = nullptr;        // [0]: done queries of the running group; [1]: zero (the sweep's LatArgs::slot_base)
   unsigned long long* came64 = nullptr;  // cells: the labels widened for vhp_planner_batch_results
   unsigned int* h_done = nullptr;        // pinned: two copies of the done word (the host's polls)
@@ -147,13 +172,15 @@ struct BatchState {
   std::vector<BatchCtl> h_ctl;
   int group = 0;                          // G of the last batch
   // set by the caller: the latency sweep of n sources cand[0 .. n) into fields out, out + cells, ... (LatArgs::slot_base: x < 0 sweeps
-  // nothing, dark cells unwritten) -- or null: the front sweep of query d (launch_planner_fronts' kernel, shape R, W, multi)
-  std::function<hipError_t(const int32_t* cand, int n, double* out)> lat_sweep;
-  std::function<hipError_t(const PlannerDev& d)> front_sweep;
+  // nothing, dark cells unwritten), source g on map map_idx[g] (device; null: one map) -- or null: the front sweep of query d on map
+  // `map` (host; 0 on one map) (launch_planner_fronts' kernel, shape R, W, multi)
+  std::function<hipError_t(const int32_t* cand, const int32_t* map_idx, int n, double* out)> lat_sweep;
+  std::function<hipError_t(const PlannerDev& d, int map)> front_sweep;
 };
 
 inline void batch_free(BatchState& s) {
-  void* dev[] = {s.vis_global, s.local[0], s.local[1], s.label, s.pivots, s.ctl, s.partial, s.ticket, s.query, s.cand, s.n_done, s.came64};
+  void* dev[] = {s.vis_global, s.local[0], s.local[1], s.label, s.pivots, s.ctl, s.partial, s.ticket, s.query, s.cand, s.map_idx, s.probe,
+                 s.n_done, s.came64};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (s.h_done) (void)hipHostFree(s.h_done);
@@ -165,7 +192,8 @@ inline void batch_free(BatchState& s) {
   s.partial = nullptr;
   s.ticket = s.n_done = s.h_done = nullptr;
   s.query = nullptr;
-  s.cand = nullptr;
+  s.cand = s.map_idx = nullptr;
+  s.probe = nullptr;
   s.came64 = nullptr;
   s.cells = s.slots = s.pivot_stride = 0;
   s.solved = false;   // (what the last batch left is gone with it)
@@ -183,9 +211,12 @@ inline int batch_epilogue_blocks(int n) {
 
 // Q queries (field coordinates) with their thresholds: status[q] / n_pivots[q] as planner_solve would give them for query q alone.
 // group: queries per group (1 .. kBatchMaxGroup; 1 where s.lat_sweep is null).  Returns VHP_OK or a call-level error.
+// On one map (stack null) its occupancy is d_occ / h_occ (m: its shape); on a stack of maps of m's shape, query q's map is
+// stack->map_idx[q] (d_occ, h_occ unused).
 inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_occ, const uint8_t* h_occ, hipStream_t stream,
                                hipEvent_t ev0, hipEvent_t ev1, const int32_t* queries, const double* thresholds, int n_queries,
-                               uint64_t max_iter, int group, int32_t* status, uint32_t* n_pivots, std::string* msg) {
+                               uint64_t max_iter, int group, int32_t* status, uint32_t* n_pivots, std::string* msg,
+                               const BatchStack* stack = nullptr) {
   const int nx = m.nx, ny = m.ny;
   const size_t cells = (size_t)nx * ny;
   s.solved = false;   // (until this batch has finished: a failed batch leaves no results)
@@ -194,17 +225,44 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   // fetched for all queries at once
   auto valid = [&](int x, int y) { return (size_t)x < (size_t)nx && (size_t)y < (size_t)ny; };
   std::vector<uint8_t> occ(2 * (size_t)n_queries, 1);
-  for (int q = 0; q < n_queries; ++q) {
-    const int32_t* p = queries + 4 * q;
-    if (!valid(p[0], p[1]) || !valid(p[2], p[3])) continue;
-    for (int e = 0; e < 2; ++e) {
-      const size_t k = (size_t)p[2 * e + 1] * nx + p[2 * e];
-      if (h_occ) occ[2 * q + e] = h_occ[k];
-      else VHP_PL_HIP(hipMemcpyAsync(&occ[2 * q + e], d_occ + k, 1, hipMemcpyDeviceToHost, stream));
+  if (stack) {  // (the bits of each query's own map, gathered on the device: one launch, one copy)
+    std::vector<int4> pts;
+    std::vector<int> at;   // the entry of occ that point i answers
+    for (int q = 0; q < n_queries; ++q) {
+      const int32_t* p = queries + 4 * q;
+      if (!valid(p[0], p[1]) || !valid(p[2], p[3])) continue;
+      for (int e = 0; e < 2; ++e) {
+        pts.push_back(make_int4(p[2 * e], p[2 * e + 1], stack->map_idx[q], 0));
+        at.push_back(2 * q + e);
+      }
     }
+    if (!pts.empty()) {
+      const int n = (int)pts.size();   // (<= 2 * kBatchMaxQueries)
+      if (!s.probe) VHP_PL_HIP(hipMalloc(&s.probe, 2 * kBatchMaxQueries * (sizeof(int4) + 1)));
+      uint8_t* d_bits = reinterpret_cast<uint8_t*>(s.probe + 2 * kBatchMaxQueries);
+      std::vector<uint8_t> bits(n);
+      VHP_PL_HIP(hipMemcpyAsync(s.probe, pts.data(), n * sizeof(int4), hipMemcpyHostToDevice, stream));
+      hipLaunchKernelGGL(vhp_planner_batch_occupancy, dim3(1), dim3(2 * kBatchMaxQueries), 0, stream, s.probe, n, stack->rows,
+                         stack->rows_stride, stack->wpr, d_bits);
+      VHP_PL_HIP(hipGetLastError());
+      VHP_PL_HIP(hipMemcpyAsync(bits.data(), d_bits, n, hipMemcpyDeviceToHost, stream));
+      VHP_PL_HIP(hipStreamSynchronize(stream));
+      for (int i = 0; i < n; ++i) occ[at[i]] = bits[i];
+    }
+  } else {
+    for (int q = 0; q < n_queries; ++q) {
+      const int32_t* p = queries + 4 * q;
+      if (!valid(p[0], p[1]) || !valid(p[2], p[3])) continue;
+      for (int e = 0; e < 2; ++e) {
+        const size_t k = (size_t)p[2 * e + 1] * nx + p[2 * e];
+        if (h_occ) occ[2 * q + e] = h_occ[k];
+        else VHP_PL_HIP(hipMemcpyAsync(&occ[2 * q + e], d_occ + k, 1, hipMemcpyDeviceToHost, stream));
+      }
+    }
+    if (!h_occ) VHP_PL_HIP(hipStreamSynchronize(stream));
   }
-  if (!h_occ) VHP_PL_HIP(hipStreamSynchronize(stream));
   std::vector<BatchQuery> run;
+  std::vector<int32_t> run_map;   // (a stack: the map of each slot)
   std::string first_msg;
   for (int q = 0; q < n_queries; ++q) {
     const int32_t* p = queries + 4 * q;
@@ -222,6 +280,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     }
     s.slot_of[q] = (int)run.size();
     run.push_back(BatchQuery{thresholds[q], p[0], p[1], p[2], p[3]});
+    run_map.push_back(stack ? stack->map_idx[q] : 0);
   }
   const size_t n_run = run.size();
   const size_t pstride = 2 * (size_t)(max_iter + 2);
@@ -242,6 +301,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
       VHP_PL_HIP(hipMalloc(&s.ticket, slots * 2 * sizeof(unsigned int)));
       VHP_PL_HIP(hipMalloc(&s.query, slots * sizeof(BatchQuery)));
       VHP_PL_HIP(hipMalloc(&s.cand, slots * 2 * sizeof(int32_t)));
+      VHP_PL_HIP(hipMalloc(&s.map_idx, slots * sizeof(int32_t)));
     }
     VHP_PL_HIP(hipMalloc(&s.n_done, 2 * sizeof(unsigned int)));
     VHP_PL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_done), 2 * sizeof(unsigned int)));
@@ -263,6 +323,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, n_run * s.pivot_stride * sizeof(int32_t), stream));
     VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, n_run * 2 * sizeof(unsigned int), stream));
     VHP_PL_HIP(hipMemcpyAsync(s.query, run.data(), n_run * sizeof(BatchQuery), hipMemcpyHostToDevice, stream));
+    if (stack) VHP_PL_HIP(hipMemcpyAsync(s.map_idx, run_map.data(), n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
   VHP_PL_HIP(hipMemsetAsync(s.n_done, 0, 2 * sizeof(unsigned int), stream));
 
@@ -312,9 +373,9 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
         const int parity = (int)(launches & 1);
         hipError_t e = hipSuccess;
         if (s.lat_sweep) {
-          e = s.lat_sweep(b.cand, n, b.local[parity]);
+          e = s.lat_sweep(b.cand, stack ? s.map_idx + g0 : nullptr, n, b.local[parity]);
         } else {
-          e = s.front_sweep(batch_query_dev(b, 0, 0));
+          e = s.front_sweep(batch_query_dev(b, 0, 0), run_map[g0]);
         }
         if (e != hipSuccess) { *msg = std::string("batch planner launch: ") + hipGetErrorString(e); return VHP_ERR_HIP; }
         hipLaunchKernelGGL(vhp_planner_batch_epilogue, dim3(blocks, n), dim3(kEpilogueThreads), 0, stream, nx, ny, b, parity);
