@@ -210,6 +210,43 @@ int vhp_planner_maps_batch_group(const vhp_ctx* ctx);
 int vhp_reconstruct_path(const uint64_t* came_from, const int32_t* pivots_xy, uint32_t n_pivots, int nx, int ny,
                          int end_x, int end_y, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length);
 
+/* reconstructPath() (solver.cpp:1183-1213) on the device, for every query of a solve at once: the labels and pivots the solves leave
+ * in device memory are walked there, and only the paths cross to the host (8 * cap + 16 bytes per query; the route through
+ * vhp_planner_[maps_]batch_results + vhp_reconstruct_path copies 8 * nx * ny bytes per query behind a widening pass).
+ *   vhp_planner_batch_paths        all Q queries of the last vhp_planner_solve_batch, in the batch's order
+ *   vhp_planner_maps_batch_paths   the same for the last vhp_planner_solve_maps_batch
+ *   vhp_planner_path               the last vhp_planner_solve / _solve_device / _solve_speculative of the context (Q = 1)
+ * For query q the outputs are exactly what vhp_reconstruct_path(came_from_q, pivots_q, n_pivots[q], nx, ny, end_q, path, cap, &n, &len)
+ * gives on the arrays the solve's host outputs / results call would copy out (the caller passes no coordinates: each query's end,
+ * n_pivots -- the solve's own count, up to max_iter + 8 after the speculative solve's fast mode -- and arrays are the context's):
+ *   path_status[q]: that call's return value.  VHP_OK; VHP_ERR_ARG for an unlabelled end (usual after VHP_ERR_MAX_ITER or
+ *     VHP_ERR_NOTHING_LIT), a label above n_pivots (device labels are uint32 with 0xFFFFFFFF for (size_t)1e15: both are above), a pivot
+ *     outside the grid or a walk of more than n_pivots + 2 hops -- the host's checks in the host's order, so no table, consistent or
+ *     not, is read out of bounds; VHP_ERR_TOO_LARGE for a path of more than cap points.  A query that failed validation (no results):
+ *     its validation code, with n_path[q] = 0 and length[q] = 0.
+ *   path_xy + 2*q*cap: the points start-first, n_path[q] of them (cap points of room per query); written only where path_status[q]
+ *     is VHP_OK.  The walk stops where the label repeats, as the host's, not "at the start".
+ *   n_path[q], length[q]: the point count and the length -- eval_d per segment, added one after the other from the start's end of the
+ *     path, so bit-identical to the host's sum.  On VHP_ERR_TOO_LARGE n_path[q] is the size needed and length[q] still the length; on
+ *     VHP_ERR_ARG both are 0 (vhp_reconstruct_path leaves its outputs alone there).
+ * path_xy may be NULL: counts and lengths only, cap ignored, no query reports VHP_ERR_TOO_LARGE.  n_path, length and path_status may
+ * each be NULL.  The call returns VHP_OK when it ran -- per-query outcomes go only into path_status --, VHP_ERR_ARG for a null context
+ * and before any such solve since the last vhp_set_map (vhp_set_maps for the maps batch), VHP_ERR_HIP on a runtime failure.
+ * The host forms copy Q * (8 * min(cap, largest n_pivots + 3) + 16) bytes in one copy and synchronise once.  The _device forms take
+ * device pointers, are asynchronous on the context's stream and write nothing but the caller's buffers.  Two small launches: a parent
+ * table (the label of every pivot's cell, one thread each) and the walks (one wavefront per query); their scratch, 12 bytes per pivot
+ * and query, belongs to the context.  No call changes any state of a solve: results, groups and vhp_last_sweep_kernel stay as they
+ * were.  Not timed: vhp_last_elapsed_ms still reports the sweep or solve before it.  The mode-2 y flip stays the caller's.
+ * (vhp_planner_solve_variant keeps host outputs and a stop rule of its own: not covered.) */
+int vhp_planner_batch_paths(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status);
+int vhp_planner_batch_paths_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length,
+                                   int32_t* d_path_status);
+int vhp_planner_maps_batch_paths(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status);
+int vhp_planner_maps_batch_paths_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length,
+                                        int32_t* d_path_status);
+int vhp_planner_path(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status);
+int vhp_planner_path_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length, int32_t* d_path_status);
+
 /* Replaces raycasting() driven over all targets as benchmark() does (solver.cpp:226-232,
  * 267-290): a Bresenham ray from the source to every cell; a blocked cell met on the way
  * zeroes that cell and the target.  out: nx*ny doubles, 1 = visible (visibilityRayCasting_,

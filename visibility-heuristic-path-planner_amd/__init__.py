@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "vhp_planner_solve_batch", "vhp_planner_batch_results_device", "vhp_planner_batch_results", "vhp_planner_batch_group",
     "vhp_set_maps", "vhp_set_maps_device", "vhp_sweep_maps_batch", "vhp_sweep_maps_batch_device",
     "vhp_planner_solve_maps_batch", "vhp_planner_maps_batch_results_device", "vhp_planner_maps_batch_results", "vhp_planner_maps_batch_group",
+    "vhp_planner_batch_paths", "vhp_planner_batch_paths_device", "vhp_planner_maps_batch_paths", "vhp_planner_maps_batch_paths_device",
+    "vhp_planner_path", "vhp_planner_path_device",
 )
 
 
@@ -105,6 +107,9 @@ def load_library():
     lib.vhp_planner_maps_batch_results_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.vhp_planner_maps_batch_results.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.vhp_planner_maps_batch_group.argtypes = [vp]
+    for name in ("vhp_planner_batch_paths", "vhp_planner_maps_batch_paths", "vhp_planner_path"):
+        getattr(lib, name).argtypes = [vp, vp, u32, vp, vp, vp]
+        getattr(lib, name + "_device").argtypes = [vp, vp, u32, vp, vp, vp]
     lib.vhp_sweep_batch_variant.argtypes = [vp, vp, i32, f64, f64, vp]
     lib.vhp_planner_solve_variant.argtypes = [vp, i32, i32, i32, i32, f64, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_sweep_batch_offset.argtypes = [vp, vp, i32, f64, vp]
@@ -157,6 +162,9 @@ class Context:
         self.stream = 0           # the stream handle last given to set_stream (0: the default stream)
         self.field_stride = 0     # the "field_stride" option as last set (vhp_set_map resets it to 0)
         self.n_maps = self.maps_nx = self.maps_ny = 0  # the stack of maps of set_maps
+        # (queries, largest n_pivots + 2) of the last batch / maps batch, and the latter of the last plain solve: the path calls' defaults
+        self._batch_q = self._maps_batch_q = (1, 2)
+        self._path_cap = 2
 
     def close(self):
         if getattr(self, "h", None):
@@ -294,6 +302,7 @@ class Context:
         npiv = C.c_uint32(0)
         rc = self.lib.vhp_planner_solve(self.h, start[0], start[1], end[0], end[1], float(threshold), int(max_iter),
                                         _ptr(came), _ptr(vg), _ptr(vl), _ptr(piv), C.byref(npiv))
+        self._path_cap = npiv.value + 2
         if rc in (VHP_ERR_HIP, VHP_ERR_NO_MAP, VHP_ERR_ARG, VHP_ERR_TOO_LARGE):
             self._check(rc)
         return dict(status=rc, came_from=came, vis_global=vg, vis_local=vl, pivots=piv[: npiv.value + 1].copy(),
@@ -311,6 +320,7 @@ class Context:
         rc = self.lib.vhp_planner_solve_speculative(self.h, start[0], start[1], end[0], end[1], float(threshold), int(max_iter), int(k), int(mode),
                                                     _ptr(came) if outputs else None, _ptr(vg) if outputs else None, _ptr(vl) if outputs else None,
                                                     _ptr(piv), C.byref(npiv), _ptr(st))
+        self._path_cap = npiv.value + 2
         if rc in (VHP_ERR_HIP, VHP_ERR_NO_MAP, VHP_ERR_ARG, VHP_ERR_TOO_LARGE):
             self._check(rc)
         return dict(status=rc, came_from=came, vis_global=vg, vis_local=vl, pivots=piv[: npiv.value + 1].copy(), n_pivots=npiv.value,
@@ -321,6 +331,7 @@ class Context:
         labels uint32 [ny, nx] (0xFFFFFFFF = unlabelled), vis_global / vis_local float64 [ny, nx], pivots int32 [n_pivots+1, 2])."""
         npiv = C.c_uint32(0)
         rc = self.lib.vhp_planner_solve_device(self.h, start[0], start[1], end[0], end[1], float(threshold), int(max_iter), C.byref(npiv))
+        self._path_cap = npiv.value + 2
         if rc in (VHP_ERR_HIP, VHP_ERR_NO_MAP, VHP_ERR_ARG, VHP_ERR_TOO_LARGE):
             self._check(rc)
         ptrs = {}
@@ -333,7 +344,8 @@ class Context:
     def planner_solve_batch(self, queries, thresholds, max_iter, outputs=True):
         """vhp_planner_solve_batch: Q independent planner_solve calls on this map in one call.  queries: [Q, 4] (start_x, start_y,
         end_x, end_y), field coordinates; thresholds: Q values or one for all.  Returns one dict per query with planner_solve's keys
-        and dtypes (outputs=False: status and n_pivots only).  A query that failed validation has pivots [[0, 0]] and None for
+        and dtypes (outputs=False: status and n_pivots only; outputs="paths": status, n_pivots, path_status, length and path -- the path
+        reconstructed on the device, no field copied: vhp_planner_batch_paths).  A query that failed validation has pivots [[0, 0]] and None for
         came_from, vis_global and vis_local, as it has no results."""
         q = np.ascontiguousarray(queries, np.int32).reshape(-1, 4)
         n = len(q)
@@ -341,7 +353,59 @@ class Context:
         st = np.zeros(n, np.int32)
         npiv = np.zeros(n, np.uint32)
         self._check(self.lib.vhp_planner_solve_batch(self.h, _ptr(q), _ptr(thr), n, int(max_iter), _ptr(st), _ptr(npiv)))
+        self._batch_q = (n, int(npiv.max()) + 2)
+        if outputs == "paths":
+            return self._batch_with_paths(st, npiv, self.lib.vhp_planner_batch_paths)
         return self._batch_outputs(st, npiv, outputs, self.nx, self.ny, self.lib.vhp_planner_batch_results)
+
+    def _paths(self, call, n, cap):
+        """One host-form path call (include/vhp.h vhp_planner_batch_paths) for n queries: a list of dict(status, length, n_path, path)
+        (n_path: the point count, also where cap was too small for it)."""
+        cap = int(cap)
+        xy = np.zeros((n, max(cap, 1), 2), np.int32)
+        cnt = np.zeros(n, np.uint32)
+        length = np.zeros(n, np.float64)
+        st = np.zeros(n, np.int32)
+        self._check(call(self.h, _ptr(xy), cap, _ptr(cnt), _ptr(length), _ptr(st)))
+        return [dict(status=int(st[q]), length=float(length[q]), n_path=int(cnt[q]),
+                     path=xy[q, : int(cnt[q])].copy() if st[q] == VHP_OK else np.zeros((0, 2), np.int32)) for q in range(n)]
+
+    def _batch_with_paths(self, st, npiv, call):
+        paths = self._paths(call, len(st), int(npiv.max()) + 2)
+        return [dict(status=int(st[q]), n_pivots=int(npiv[q]), path_status=p["status"], length=p["length"], path=p["path"])
+                for q, p in enumerate(paths)]
+
+    def planner_batch_paths(self, cap=None):
+        """vhp_planner_batch_paths: the paths of the queries of the last planner_solve_batch, reconstructed on the device.  A list of
+        dict(status, length, path) -- path int32 [n_path, 2], start first, empty where status is not VHP_OK.  cap: points of room per
+        query (default: the largest n_pivots + 2 of the solve)."""
+        n, dflt = self._batch_q
+        return self._paths(self.lib.vhp_planner_batch_paths, n, dflt if cap is None else cap)
+
+    def planner_batch_paths_device(self, d_path_xy, cap, d_n_path=0, d_length=0, d_status=0):
+        """vhp_planner_batch_paths_device: raw device pointers (0: not wanted), asynchronous on the context stream."""
+        self._check(self.lib.vhp_planner_batch_paths_device(self.h, C.c_void_p(d_path_xy or None), int(cap), C.c_void_p(d_n_path or None),
+                                                            C.c_void_p(d_length or None), C.c_void_p(d_status or None)))
+
+    def planner_maps_batch_paths(self, cap=None):
+        """vhp_planner_maps_batch_paths: planner_batch_paths for the last planner_solve_maps_batch."""
+        n, dflt = self._maps_batch_q
+        return self._paths(self.lib.vhp_planner_maps_batch_paths, n, dflt if cap is None else cap)
+
+    def planner_maps_batch_paths_device(self, d_path_xy, cap, d_n_path=0, d_length=0, d_status=0):
+        """vhp_planner_maps_batch_paths_device (see planner_batch_paths_device)."""
+        self._check(self.lib.vhp_planner_maps_batch_paths_device(self.h, C.c_void_p(d_path_xy or None), int(cap), C.c_void_p(d_n_path or None),
+                                                                 C.c_void_p(d_length or None), C.c_void_p(d_status or None)))
+
+    def planner_path(self, cap=None):
+        """vhp_planner_path: the path of the last planner_solve / planner_solve_device / planner_solve_speculative, reconstructed on
+        the device: dict(status, length, path)."""
+        return self._paths(self.lib.vhp_planner_path, 1, self._path_cap if cap is None else cap)[0]
+
+    def planner_path_device(self, d_path_xy, cap, d_n_path=0, d_length=0, d_status=0):
+        """vhp_planner_path_device (see planner_batch_paths_device)."""
+        self._check(self.lib.vhp_planner_path_device(self.h, C.c_void_p(d_path_xy or None), int(cap), C.c_void_p(d_n_path or None),
+                                                     C.c_void_p(d_length or None), C.c_void_p(d_status or None)))
 
     def _batch_outputs(self, st, npiv, outputs, nx, ny, results):
         n = len(st)
@@ -384,6 +448,9 @@ class Context:
         st = np.zeros(n, np.int32)
         npiv = np.zeros(n, np.uint32)
         self._check(self.lib.vhp_planner_solve_maps_batch(self.h, _ptr(q), _ptr(idx), _ptr(thr), n, int(max_iter), _ptr(st), _ptr(npiv)))
+        self._maps_batch_q = (n, int(npiv.max()) + 2)
+        if outputs == "paths":
+            return self._batch_with_paths(st, npiv, self.lib.vhp_planner_maps_batch_paths)
         return self._batch_outputs(st, npiv, outputs, self.maps_nx, self.maps_ny, self.lib.vhp_planner_maps_batch_results)
 
     def planner_maps_batch_results_device(self, q):

@@ -22,6 +22,7 @@
 #include "vhp_sweep.hip.h"
 #include "vhp_planner.hip.h"
 #include "vhp_planner_batch.hip.h"
+#include "vhp_paths.hip.h"
 #include "vhp_queue.hip.h"
 #include "vhp_variant.hip.h"
 #include "vhp_union.hip.h"
@@ -109,6 +110,7 @@ struct vhp_ctx {
   uint64_t* d_maps_dmap = nullptr;  // every map's diagonal maps (map k's k * lat_diag_map_bytes further): built by the first planner batch
                                     // on the stack that takes the latency sweep (vhp_planner_solve_maps_batch), kept until the stack goes
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
+  vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
 };
 
 namespace {
@@ -571,6 +573,85 @@ int batch_slot(vhp_ctx* ctx, const char* who, int q, int* slot, bool maps = fals
   return VHP_OK;
 }
 
+// A plain or speculative solve that returned before it ran (one of the four validation codes, or VHP_ERR_ARG): vhp_planner_path
+// reports that code for its query.
+void note_unsolved(vhp_ctx* ctx, int rc) {
+  if (rc == VHP_ERR_ARG || (rc >= VHP_ERR_START_OOB && rc <= VHP_ERR_END_OCCUPIED)) {
+    ctx->pl.path_state = 2;
+    ctx->pl.last_code = rc;
+  }
+}
+
+// What a path call reads of the last batch on b (nx x ny): every query's slot or validation code, its n_pivots, the slots' arrays.
+vhp::PathsDev batch_paths_dev(const vhp::BatchState& b, const std::vector<int32_t>& codes, int nx, int ny) {
+  vhp::PathsDev p{};
+  p.label = b.label;
+  p.pivots = b.pivots;
+  p.label_stride = b.cells;
+  p.pivot_stride = b.pivot_stride;
+  p.query = b.query;
+  p.nx = nx;
+  p.ny = ny;
+  p.n_queries = (int)b.slot_of.size();
+  for (int q = 0; q < p.n_queries; ++q) {
+    const int k = b.slot_of[q];
+    p.slot[q] = (int16_t)(k >= 0 ? k : -codes[q]);
+    p.nb[q] = k >= 0 ? (uint32_t)b.h_ctl[k].ctl.nb : 0u;
+  }
+  return p;
+}
+
+// The last plain / speculative solve as a batch of one.
+vhp::PathsDev plain_paths_dev(const vhp_ctx* ctx) {
+  const vhp::PlannerState& s = ctx->pl;
+  vhp::PathsDev p{};
+  p.label = s.label;
+  p.pivots = s.pivots;
+  p.query = nullptr;
+  p.end_x = s.last_end_x;
+  p.end_y = s.last_end_y;
+  p.nx = ctx->nx;
+  p.ny = ctx->ny;
+  p.n_queries = 1;
+  p.slot[0] = (int16_t)(s.path_state == 1 ? 0 : -s.last_code);
+  p.nb[0] = s.path_state == 1 ? s.last_nb : 0u;
+  return p;
+}
+
+// The six path entry points behind one body: the device form launches into the caller's buffers, the host form through staging.
+int paths_call(vhp_ctx* ctx, const char* who, vhp::PathsDev p, bool device, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length,
+               int32_t* path_status) {
+  VHP_ON_DEVICE(ctx);
+  hipError_t e;
+  if (device) {
+    p.path_xy = path_xy;
+    p.cap = cap;
+    p.n_path = n_path;
+    p.length = length;
+    p.status = path_status;
+    e = vhp::paths_launch(ctx->paths, p, ctx->stream);
+  } else {
+    e = vhp::paths_host(ctx->paths, p, ctx->stream, path_xy, cap, n_path, length, path_status);
+  }
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return VHP_OK;
+}
+
+int batch_paths(vhp_ctx* ctx, const char* who, bool maps, bool device, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length,
+                int32_t* path_status) {
+  if (!ctx) return VHP_ERR_ARG;
+  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
+  return paths_call(ctx, who, batch_paths_dev(b, b.codes, maps ? ctx->maps_nx : ctx->nx, maps ? ctx->maps_ny : ctx->ny), device, path_xy, cap,
+                    n_path, length, path_status);
+}
+
+int plain_path(vhp_ctx* ctx, const char* who, bool device, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {
+  if (!ctx) return VHP_ERR_ARG;
+  if (ctx->pl.path_state == 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": no planner solve has run on this map");
+  return paths_call(ctx, who, plain_paths_dev(ctx), device, path_xy, cap, n_path, length, path_status);
+}
+
 }  // namespace
 
 extern "C" {
@@ -607,6 +688,7 @@ int vhp_destroy(vhp_ctx* ctx) {
   hipStreamSynchronize(ctx->stream);
   free_map(ctx);
   free_maps(ctx);
+  vhp::paths_free(ctx->paths);
   for (void* p : {(void*)ctx->d_src, (void*)ctx->d_map_idx, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
     if (p) (void)hipFree(p);
   for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1175,8 +1257,10 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
         return e;
       };
   }
+  ctx->pl.path_state = 0;
   int rc = vhp::planner_solve(ctx->pl, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x,
                               end_y, threshold, max_iter, came_from, vis_global, vis_local, pivots_xy, n_pivots, &msg);
+  note_unsolved(ctx, rc);
   ctx->timed = true;
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
@@ -1215,9 +1299,11 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
       };
   }
   int st[3] = {0, 0, 0};
+  ctx->pl.path_state = 0;
   int rc = vhp::planner_solve_speculative(ctx->pl, ctx->spec, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y,
                                           threshold, max_iter, k, mode, came_from, vis_global, vis_local, pivots_xy, n_pivots, st, &msg);
   if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2]; }
+  note_unsolved(ctx, rc);
   ctx->timed = true;
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
@@ -1398,6 +1484,26 @@ int vhp_planner_maps_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, dou
   const int rc = vhp::batch_results_host(ctx->maps_batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
+}
+
+int vhp_planner_batch_paths(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {
+  return batch_paths(ctx, "vhp_planner_batch_paths", false, false, path_xy, cap, n_path, length, path_status);
+}
+int vhp_planner_batch_paths_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length, int32_t* d_path_status) {
+  return batch_paths(ctx, "vhp_planner_batch_paths_device", false, true, d_path_xy, cap, d_n_path, d_length, d_path_status);
+}
+int vhp_planner_maps_batch_paths(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {
+  return batch_paths(ctx, "vhp_planner_maps_batch_paths", true, false, path_xy, cap, n_path, length, path_status);
+}
+int vhp_planner_maps_batch_paths_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length,
+                                        int32_t* d_path_status) {
+  return batch_paths(ctx, "vhp_planner_maps_batch_paths_device", true, true, d_path_xy, cap, d_n_path, d_length, d_path_status);
+}
+int vhp_planner_path(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {
+  return plain_path(ctx, "vhp_planner_path", false, path_xy, cap, n_path, length, path_status);
+}
+int vhp_planner_path_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length, int32_t* d_path_status) {
+  return plain_path(ctx, "vhp_planner_path_device", true, d_path_xy, cap, d_n_path, d_length, d_path_status);
 }
 
 // eval_d of visibilityBasedSolver.h:112-115 (host side, used only for the path length)

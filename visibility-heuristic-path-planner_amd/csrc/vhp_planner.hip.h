@@ -97,6 +97,12 @@ struct PlannerState {
   PlannerCtl* h_ctl = nullptr;
   hipEvent_t poll_ev[2] = {nullptr, nullptr};
   const uint8_t* h_occ = nullptr;   // the caller's host copy of the map if it has one (vhp_set_map), for the start / end validation
+  // what the last solve on this state left for vhp_planner_path: 0 nothing (no solve since the map was set, or one that failed in the
+  // runtime), 1 results with last_nb pivots for a query that ends in (last_end_x, last_end_y), 2 none -- the solve returned last_code
+  // (a validation code) before it ran
+  int path_state = 0, last_code = 0;
+  uint32_t last_nb = 0;
+  int last_end_x = 0, last_end_y = 0;
   // launch shape of the front sweep and the per-device dynamic-LDS bookkeeping, set by the caller (vhp_capi.hip)
   int R = 2, W = 8;
   bool multi = false;
@@ -128,6 +134,7 @@ inline void planner_free(PlannerState& s) {
   for (auto& e : s.poll_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   s.cells = 0;
   s.pivot_cap = 0;
+  s.path_state = 0;
   s.vis_global = s.vis_local = nullptr;
   s.label = nullptr;
   s.came64 = nullptr;
@@ -308,6 +315,10 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
   s.vis_local_out = (two_fields && ctl.iters > 0 && ((ctl.iters - 1) & 1)) ? s.vis_local2 : s.vis_local;
   const uint32_t nb = (uint32_t)ctl.nb;
   if (n_pivots) *n_pivots = nb;
+  s.path_state = 1;
+  s.last_nb = nb;
+  s.last_end_x = end_x;
+  s.last_end_y = end_y;
   if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, s.pivots, 2 * (size_t)(nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   if (came_from) {
     hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, s.label, s.came64, cells);
@@ -860,6 +871,10 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
 
   const uint32_t nb = (uint32_t)ctl.nb;
   if (n_pivots) *n_pivots = nb;
+  s.path_state = 1;
+  s.last_nb = nb;
+  s.last_end_x = end_x;
+  s.last_end_y = end_y;
   if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, s.pivots, 2 * (size_t)(nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   if (came_from) {
     hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, s.label, s.came64, cells);

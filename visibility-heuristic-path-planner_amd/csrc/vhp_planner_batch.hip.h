@@ -169,6 +169,7 @@ struct BatchState {
   bool solved = false;
   bool two_fields = false;
   std::vector<int> slot_of;
+  std::vector<int32_t> codes;             // per query: the validation code of one without a slot (vhp_planner_batch_paths reports it)
   std::vector<BatchCtl> h_ctl;
   int group = 0;                          // G of the last batch
   // set by the caller: the latency sweep of n sources cand[0 .. n) into fields out, out + cells, ... (LatArgs::slot_base: x < 0 sweeps
@@ -221,6 +222,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   const size_t cells = (size_t)nx * ny;
   s.solved = false;   // (until this batch has finished: a failed batch leaves no results)
   s.slot_of.assign(n_queries, -1);
+  s.codes.assign(n_queries, VHP_OK);
   // the four validity checks of solve() per query, in the reference's order (solver.cpp:89-116); the occupancy of a device map is
   // fetched for all queries at once
   auto valid = [&](int x, int y) { return (size_t)x < (size_t)nx && (size_t)y < (size_t)ny; };
@@ -274,6 +276,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     else if (!occ[2 * q + 1]) { st = VHP_ERR_END_OCCUPIED; why = "End point is not valid (occupied)"; }
     status[q] = st;
     n_pivots[q] = 0;
+    s.codes[q] = st;
     if (why) {
       if (first_msg.empty()) first_msg = "query " + std::to_string(q) + ": " + why;
       continue;
