@@ -247,6 +247,55 @@ int vhp_planner_maps_batch_paths_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32
 int vhp_planner_path(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status);
 int vhp_planner_path_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length, int32_t* d_path_status);
 
+/* The whole tree of a solve, read from any cell: path lengths to every cell (a cost-to-come field per query) and paths to any goal.
+ * A solve leaves a tree in device memory, not one path: every cell some pivot lit carries that pivot's label, every pivot's own cell the
+ * label of the pivot that lit it.  The path calls above walk it from each query's `end` only; these walk it from any cell -- one start,
+ * many goals -- and replace the reference's interface.m:141-162 (back-tracking cameFrom + pivots from a point the user chooses).
+ * `solve` selects whose tree (vhp_solve_kind): VHP_SOLVE_PLAIN the last vhp_planner_solve / _solve_device / _solve_speculative of the
+ * context (Q = 1), VHP_SOLVE_BATCH the last vhp_planner_solve_batch, VHP_SOLVE_MAPS_BATCH the last vhp_planner_solve_maps_batch;
+ * lifetimes are those of the path calls (until the next such solve or vhp_set_map; vhp_set_maps for the maps batch).
+ * For query q and cell (x, y) everything reported is exactly what
+ *   vhp_reconstruct_path(came_from_q, pivots_q, n_pivots[q], nx, ny, x, y, path, cap, &n, &len)
+ * gives on the arrays the solve's host outputs / results call would copy out: return value, point count, points, and the fp64 bits of
+ * the length (eval_d per segment, added one after the other from the start's end of the path).  That call returns VHP_ERR_ARG for an
+ * unlabelled cell (blocked cells and cells no pivot lit; usual far from the path, and everywhere unlit after VHP_ERR_MAX_ITER), a label
+ * above n_pivots, a pivot outside the grid anywhere on the chain, and labels that form a cycle -- the host's checks, so no table,
+ * consistent or not, is read out of bounds or walked without bound.
+ *   vhp_planner_length_fields: queries q_first .. q_first + n_q - 1; each gets nx * ny doubles in `length` and nx * ny uint32 in `n_path`,
+ *     packed, row-major, in query order (query q's field at (q - q_first) * nx * ny).  Either output may be NULL.  A cell whose call
+ *     would return VHP_OK gets its length and point count (2 + the depth of its label in the tree); every other cell gets length = -1.0
+ *     and n_path = 0; a query that failed validation (no results) gets that filler everywhere.  Returns VHP_OK when it ran;
+ *     VHP_ERR_ARG for a null context, a selector that is no vhp_solve_kind, a range outside 0..Q-1 (n_q < 1 included), both outputs
+ *     NULL, and before any such solve; VHP_ERR_HIP on a runtime failure.
+ *   vhp_planner_goal_paths: goal g is the triple goals_qxy[3g .. 3g+2] = {q, x, y}; outputs per goal as vhp_planner_batch_paths' per query.
+ *     path_status[g]: VHP_OK, VHP_ERR_ARG or VHP_ERR_TOO_LARGE as that call returns them; VHP_ERR_END_OOB for a goal outside the grid
+ *     (the host call returns it before it walks); for a query without results its validation code, whatever the goal.  path_xy +
+ *     2*g*cap: the points start-first, written only where path_status[g] is VHP_OK.  On VHP_ERR_TOO_LARGE n_path[g] is the size needed
+ *     and length[g] still the length; on every other status but VHP_OK both are 0.  path_xy may be NULL: counts and lengths only, cap
+ *     ignored, no goal reports VHP_ERR_TOO_LARGE.  n_path, length and path_status may each be NULL.  A q outside 0..Q-1: the host form
+ *     checks every goal first and fails the call with VHP_ERR_ARG, nothing written; the _device form gives that goal the status
+ *     VHP_ERR_ARG.  n_goals = 0 is VHP_OK with nothing written; n_goals < 0 or null goals: VHP_ERR_ARG.  Otherwise the call returns as
+ *     vhp_planner_length_fields does -- per-goal outcomes go only into path_status.
+ * The _device forms take device pointers (aligned to their element types, else VHP_ERR_ARG), are asynchronous on the context's stream
+ * and write nothing but the caller's buffers -- asynchronous once the context's scratch has reached its size: the first call, and any
+ * call with more pivots or queries than every call before it, frees and allocates the scratch, which waits for the device (as for the
+ * path calls).  The host forms stage the results in device memory and synchronise once: length_fields makes one copy per output asked
+ * for, straight into the caller's arrays (8 and 4 bytes per cell); goal_paths makes ONE copy of n_goals * (8 * min(cap, largest
+ * n_pivots + 3) + 16) bytes.  Per call: one small launch that builds a
+ * table of every pivot's depth, validity and running length from the root (20 bytes per pivot with its coordinates, plus its parent;
+ * rebuilt every call, never cached; scratch of the context), then one streaming launch over the cells -- one label load, one table
+ * lookup, one eval_d, one store per cell; fields that start on a 16-byte boundary are read and written 16 bytes at a time -- or one
+ * thread per goal.  No call changes any state of a solve: results, groups and vhp_last_sweep_kernel stay as they were.  Not timed:
+ * vhp_last_elapsed_ms still reports the sweep or solve before it.  The mode-2 y flip stays the caller's.
+ * (vhp_planner_solve_variant keeps host outputs and a stop rule of its own: not covered.) */
+typedef enum vhp_solve_kind { VHP_SOLVE_PLAIN = 0, VHP_SOLVE_BATCH = 1, VHP_SOLVE_MAPS_BATCH = 2 } vhp_solve_kind;
+int vhp_planner_length_fields(vhp_ctx* ctx, int solve, int q_first, int n_q, double* length, uint32_t* n_path);
+int vhp_planner_length_fields_device(vhp_ctx* ctx, int solve, int q_first, int n_q, double* d_length, uint32_t* d_n_path);
+int vhp_planner_goal_paths(vhp_ctx* ctx, int solve, const int32_t* goals_qxy, int n_goals, int32_t* path_xy, uint32_t cap,
+                           uint32_t* n_path, double* length, int32_t* path_status);
+int vhp_planner_goal_paths_device(vhp_ctx* ctx, int solve, const int32_t* d_goals_qxy, int n_goals, int32_t* d_path_xy, uint32_t cap,
+                                  uint32_t* d_n_path, double* d_length, int32_t* d_path_status);
+
 /* Replaces raycasting() driven over all targets as benchmark() does (solver.cpp:226-232,
  * 267-290): a Bresenham ray from the source to every cell; a blocked cell met on the way
  * zeroes that cell and the target.  out: nx*ny doubles, 1 = visible (visibilityRayCasting_,

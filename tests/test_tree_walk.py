@@ -1,0 +1,302 @@
+"""The tree calls' bodies (csrc/vhp_tree.hpp: the per-pivot tables, the per-cell result of the length field and the per-goal path that
+vhp_tree.hip.h's kernels wrap), built with the host compiler into tests/tree_driver.cpp and held to vhp_reconstruct_path from the same
+cell -- status, point count, every point and the length's float64 bits, by == -- at EVERY cell of planner results of the CPU oracle
+and on constructed tables that are not planner results.  No GPU.
+The driver is built twice: plain, and with the address and undefined-behaviour sanitizers (every buffer there has exactly the size the
+header asks for); every case runs through both.
+Non-vacuity: in every whole-grid case at least half of the cells are ones where vhp_reconstruct_path on the ORACLE's arrays returns
+VHP_OK and at least a quarter have a path of three or more points (asserted; the maps, seeds and thresholds were chosen with the
+oracle so that it holds: a solve stops when it sees its end, so only far-apart starts and ends light most of a map)."""
+import ctypes as C
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import maps
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "visibility-heuristic-path-planner_amd", "csrc")
+DRIVER = os.path.join(HERE, "tree_driver.cpp")
+UNL32 = 0xFFFFFFFF
+UNL64 = 1000000000000000
+OK, ERR_ARG, ERR_END_OOB, ERR_MAX_ITER, ERR_TOO_LARGE = 0, 1, 11, 20, 102
+ALL = None   # goals: every cell of the grid
+
+
+@pytest.fixture(scope="module")
+def drivers(tmp_path_factory):
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler (set CXX)"
+    d = str(tmp_path_factory.mktemp("tree_driver"))
+    exes = []
+    for name, extra in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = os.path.join(d, "tree_driver_" + name)
+        subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off"] + extra + ["-I", CSRC, "-o", exe, DRIVER])
+        exes.append(exe)
+    return exes
+
+
+@pytest.fixture(scope="module")
+def vhp():
+    import vhp_amd
+    vhp_amd.build_library()
+    vhp_amd.load_library()
+    return vhp_amd
+
+
+def _labels32(came):
+    """the device's labels for the host's: uint32, 0xFFFFFFFF where the reference holds (size_t)1e15"""
+    came = np.asarray(came, np.uint64)
+    return np.where(came >= np.uint64(UNL32), np.uint64(UNL32), came).astype(np.uint32)
+
+
+def _goal_list(goals, nx, ny):
+    return [(x, y) for y in range(ny) for x in range(nx)] if goals is ALL else [(int(x), int(y)) for x, y in goals]
+
+
+def _host(vhp, came, pivots, goals, cap):
+    """vhp_reconstruct_path itself from every goal: [(status, n_path, length bits, points, True)] -- n_path and length start at 0, as the
+    driver reports them where the host leaves its outputs alone; the points are those written (none unless VHP_OK with a buffer)."""
+    lib = vhp.load_library()
+    came = np.ascontiguousarray(came, np.uint64)
+    ny, nx = came.shape
+    piv = np.ascontiguousarray(pivots, np.int32).reshape(-1, 2)
+    path = np.empty((max(cap, 0), 2), np.int32)
+    pc, pp = came.ctypes.data_as(C.c_void_p), piv.ctypes.data_as(C.c_void_p)
+    pb = path.ctypes.data_as(C.c_void_p) if cap >= 0 else None
+    out = []
+    for x, y in _goal_list(goals, nx, ny):
+        n, d = C.c_uint32(0), C.c_double(0.0)
+        path[:] = -777
+        rc = lib.vhp_reconstruct_path(pc, pp, len(piv) - 1, nx, ny, x, y, pb, max(cap, 0), C.byref(n), C.byref(d))
+        written = n.value if rc == OK and cap >= 0 else 0
+        assert (path[written:] == -777).all()
+        out.append((rc, n.value, struct.pack("<d", d.value).hex(), path[:written].reshape(-1).tolist(), True))
+    return out
+
+
+def _run(drivers, tables):
+    """tables: [(labels uint32 [ny, nx], pivots [n + 1, 2], goals or ALL, cap)] -> per table the driver's rows (status, n_path, length
+    bits, points, buffer otherwise untouched) and the length field's (n_path, length bits) per goal"""
+    blob = b""
+    counts = []
+    for lab, piv, goals, cap in tables:
+        lab = np.ascontiguousarray(lab, np.uint32)
+        piv = np.ascontiguousarray(piv, np.int32).reshape(-1, 2)
+        ny, nx = lab.shape
+        g = np.zeros((0, 2), np.int32) if goals is ALL else np.ascontiguousarray(goals, np.int32).reshape(-1, 2)
+        counts.append(nx * ny if goals is ALL else len(g))
+        blob += struct.pack("<5i", nx, ny, len(piv) - 1, cap, -1 if goals is ALL else len(g)) + lab.tobytes() + piv.tobytes() + g.tobytes()
+    outs = []
+    for exe in drivers:
+        p = subprocess.run([exe], input=blob, capture_output=True, check=False)
+        assert p.returncode == 0, (exe, p.returncode, p.stderr.decode()[-2000:])
+        outs.append(p.stdout)
+    assert outs[0] == outs[1], "the sanitizer build and the plain build disagree"
+    rows, fields = [], []
+    for line in outs[0].decode().splitlines():
+        f = line.split()
+        rows.append((int(f[0]), int(f[1]), struct.pack("<Q", int(f[2], 16)).hex(), [int(v) for v in f[6:]], f[3] == "1"))
+        fields.append((int(f[4]), struct.pack("<Q", int(f[5], 16)).hex()))
+    assert len(rows) == sum(counts)
+    per_table, at = [], 0
+    for c in counts:
+        per_table.append((rows[at: at + c], fields[at: at + c]))
+        at += c
+    return per_table
+
+
+FILLER = (0, struct.pack("<d", -1.0).hex())
+
+
+def _compare(vhp, drivers, tables):
+    """tables: [(came_from uint64 [ny, nx], pivots, goals or ALL, cap)]: the driver on the device's form of each against
+    vhp_reconstruct_path from every goal; the length field's cell must say the same (filler where the call is not VHP_OK / TOO_LARGE).
+    Returns per table the reference's rows."""
+    got = _run(drivers, [(_labels32(c), p, g, cap) for c, p, g, cap in tables])
+    wants = []
+    for k, ((rows, fields), (came, piv, goals, cap)) in enumerate(zip(got, tables)):
+        want = _host(vhp, came, piv, goals, cap)
+        ny, nx = came.shape
+        for (x, y), g, f, w in zip(_goal_list(goals, nx, ny), rows, fields, want):
+            assert g == w, "table %d, goal (%d, %d), cap %d: tree_goal_path %r, vhp_reconstruct_path %r" % (k, x, y, cap, g, w)
+            if w[0] in (OK, ERR_TOO_LARGE):
+                assert f == (w[1], w[2]), "table %d, cell (%d, %d): field %r, host %r" % (k, x, y, f, w[:3])
+            elif w[0] == ERR_ARG:
+                assert f == FILLER, "table %d, cell (%d, %d): field %r where the host returns VHP_ERR_ARG" % (k, x, y, f)
+        wants.append(want)
+    return wants
+
+
+def _not_vacuous(want, what):
+    ok = sum(1 for w in want if w[0] == OK)
+    long_paths = sum(1 for w in want if w[0] == OK and w[1] >= 3)
+    assert 2 * ok >= len(want), "%s: only %d of %d cells have a path" % (what, ok, len(want))
+    assert 4 * long_paths >= len(want), "%s: only %d of %d cells have a path of three or more points" % (what, long_paths, len(want))
+
+
+def _corner_map(seed):
+    occ = maps.random_rect_map(100, 100, 25, 2, 20, 2, 20, seed=seed)
+    occ[5, 5] = occ[95, 95] = 1
+    return occ
+
+
+@pytest.mark.parametrize("seed", [100, 101, 103, 105])
+def test_every_cell_of_random_maps(vhp, oracle, drivers, seed):
+    """100 x 100 maps of 25 rectangles, (5, 5) -> (95, 95), threshold 0.25: solved ones (3 to 9 pivots) and one that live-locks until
+    max_iter (251 pivots, most of them repeats of one cell: a deep chain)."""
+    occ = _corner_map(seed)
+    r = oracle.solve(occ, (5, 5), (95, 95), 0.25, 250)
+    assert r["status"] == (ERR_MAX_ITER if seed == 100 else OK)
+    want, = _compare(vhp, drivers, [(r["came_from"], r["pivots"], ALL, r["n_pivots"] + 3)])
+    _not_vacuous(want, "seed %d" % seed)
+    if r["status"] == OK:
+        d, path = oracle.reconstruct_path(r["came_from"], r["pivots"], (95, 95))
+        w = want[95 * 100 + 95]
+        assert w[0] == OK and struct.unpack("<d", bytes.fromhex(w[2]))[0] == d and w[3] == path.reshape(-1).tolist()
+    assert any(w[0] == ERR_ARG for w in want)   # (blocked cells are unlabelled)
+
+
+def test_every_cell_after_max_iter(vhp, oracle, drivers):
+    """max_iter 3: the solve stops with VHP_ERR_MAX_ITER, its end unlabelled, the tree four pivots deep at most."""
+    occ = _corner_map(104)
+    r = oracle.solve(occ, (5, 5), (95, 95), 0.25, 3)
+    assert r["status"] == ERR_MAX_ITER and r["n_pivots"] == 4
+    want, = _compare(vhp, drivers, [(r["came_from"], r["pivots"], ALL, r["n_pivots"] + 3)])
+    _not_vacuous(want, "max_iter 3")
+    assert want[95 * 100 + 95][0] == ERR_ARG
+
+
+def test_every_cell_of_a_maze_crop(vhp, oracle, drivers):
+    """A 160 x 130 crop of maze_6, threshold 0.1, a query across it: 251 pivots."""
+    occ = np.ascontiguousarray(maps.maze_6()[50:180, 200:360])
+    r = oracle.solve(occ, (62, 32), (38, 126), 0.1, 250)
+    assert r["status"] in (OK, ERR_MAX_ITER) and r["n_pivots"] >= 64
+    want, = _compare(vhp, drivers, [(r["came_from"], r["pivots"], ALL, r["n_pivots"] + 3)])
+    _not_vacuous(want, "maze crop")
+    assert max(w[1] for w in want) >= 8
+
+
+def _table(nx, ny, pivots, parents, cells=()):
+    """came_from with pivot k's cell labelled parents[k] (None: unlabelled) and further (x, y, label) cells"""
+    came = np.full((ny, nx), UNL64, np.uint64)
+    for (x, y), t in zip(pivots, parents):
+        if t is not None and 0 <= x < nx and 0 <= y < ny:
+            came[y, x] = t
+    for x, y, t in cells:
+        came[y, x] = t
+    return came
+
+
+def test_constructed_tables(vhp, drivers):
+    nx, ny = 23, 17
+    chain = [(1, 1), (5, 2), (9, 7), (14, 3), (20, 12)]           # pivot k lit by pivot k - 1, the start labels itself
+    par = [0, 0, 1, 2, 3]
+    n = len(chain) - 1
+    # one cell per label 0 .. 6 (5 and 6 are above n_pivots), the rest unlabelled; every goal list below visits them all
+    cells = [(2 + 3 * t, 15, t) for t in range(7)] + [(22, 16, 0xFFFFFFFE)]
+    probes = [(x, y) for x, y, _ in cells] + chain + [(0, 0)]
+    oob = [(-1, 3), (nx, 3), (4, -1), (4, ny), (-5, -5)]
+    big = 70
+    long_piv = [(1 + k % 20, 1 + 2 * (k // 20)) for k in range(big + 1)]
+    long_cells = [(21, 2 * (k % 8), k) for k in (0, 1, 35, big - 1, big)]
+    long_probes = [(x, y) for x, y, _ in long_cells] + long_piv
+    shuffled = [3, 3, 4, 3, 0]   # the root is pivot 3; parent[t] > t for 0, 1, 2: 4 -> 0 -> 3, 2 -> 4
+    cases = {
+        "good": (_table(nx, ny, chain, par, cells), chain, probes, n + 3),
+        "good, every cell": (_table(nx, ny, chain, par, cells), chain, ALL, n + 3),
+        "cap exact": (_table(nx, ny, chain, par, cells), chain, probes, 6),
+        "cap one too small": (_table(nx, ny, chain, par, cells), chain, probes, 5),
+        "cap zero": (_table(nx, ny, chain, par, cells), chain, probes, 0),
+        "no path buffer": (_table(nx, ny, chain, par, cells), chain, probes, -1),
+        "goals outside the grid": (_table(nx, ny, chain, par, cells), chain, oob, n + 3),
+        "unlabelled pivot": (_table(nx, ny, chain, [0, 0, None, 2, 3], cells), chain, probes, n + 3),
+        "two-cycle": (_table(nx, ny, chain, [0, 2, 1, 2, 3], cells), chain, probes, n + 3),
+        "two-cycle at the root": (_table(nx, ny, chain, [1, 0, 1, 2, 3], cells), chain, probes, n + 3),
+        "long cycle": (_table(nx, ny, long_piv, [(k + 1) % (big + 1) for k in range(big + 1)], long_cells), long_piv, long_probes, big + 3),
+        "long cycle with a tail": (_table(nx, ny, long_piv, [10] + list(range(big)), long_cells), long_piv, long_probes, big + 3),
+        "root other than 0": (_table(nx, ny, chain, [2, 0, 2, 2, 3], cells), chain, probes, n + 3),
+        "parent above child": (_table(nx, ny, chain, shuffled, cells), chain, probes, n + 3),
+        "two roots": (_table(nx, ny, chain, [0, 0, 1, 3, 3], cells), chain, probes, n + 3),
+        "pivot outside the grid at the root": (_table(nx, ny, [(nx, 1)] + chain[1:], par, cells), [(nx, 1)] + chain[1:], probes, n + 3),
+        "pivot outside the grid in mid-chain": (_table(nx, ny, chain[:2] + [(9, -1)] + chain[3:], par, cells), chain[:2] + [(9, -1)] + chain[3:],
+                                                probes, n + 3),
+        "label of a pivot above n_pivots": (_table(nx, ny, chain, [0, 0, 9, 2, 3], cells), chain, probes, n + 3),
+        "n_pivots = 0": (_table(nx, ny, [(3, 3)], [0], [(8, 9, 0), (9, 9, 1)]), [(3, 3)], [(8, 9), (9, 9), (3, 3), (0, 0)], 3),
+        "longest consistent chain": (_table(nx, ny, long_piv, [max(k - 1, 0) for k in range(big + 1)], long_cells), long_piv, long_probes, big + 2),
+        "longest chain, cap one too small": (_table(nx, ny, long_piv, [max(k - 1, 0) for k in range(big + 1)], long_cells), long_piv, long_probes,
+                                             big + 1),
+    }
+    names = sorted(cases)
+    got = dict(zip(names, _compare(vhp, drivers, [cases[k] for k in names])))
+    at = {p: k for k, p in enumerate(probes)}
+    good = got["good"]
+    # the cell labelled 4: the whole chain and the cell
+    assert good[at[(14, 15)]][:2] == (OK, 6) and good[at[(14, 15)]][3] == [1, 1, 5, 2, 9, 7, 14, 3, 20, 12, 14, 15]
+    assert good[at[(2, 15)]][:2] == (OK, 2) and good[at[(2, 15)]][3] == [1, 1, 2, 15]
+    assert good[at[(1, 1)]][:3] == (OK, 2, struct.pack("<d", 0.0).hex())           # the start itself: two points, length 0
+    assert [good[at[p]][0] for p in ((17, 15), (20, 15), (22, 16), (0, 0))] == [ERR_ARG] * 4   # labels 5, 6, 0xFFFFFFFE, unlabelled
+    assert sum(w[0] == OK for w in got["good, every cell"]) == 5 + 5
+    assert {w[0] for w in got["cap exact"]} == {OK, ERR_ARG}
+    small = got["cap one too small"][at[(14, 15)]]
+    assert small[:2] == (ERR_TOO_LARGE, 6) and small[2] == good[at[(14, 15)]][2] and small[3] == []
+    assert got["cap one too small"][at[(11, 15)]][:2] == (OK, 5)
+    assert {w[0] for w in got["cap zero"]} == {ERR_TOO_LARGE, ERR_ARG}
+    assert [w[:3] for w in got["no path buffer"]] == [w[:3] for w in good]
+    assert [w[:2] for w in got["goals outside the grid"]] == [(ERR_END_OOB, 0)] * len(oob)
+    assert {w[0] for w in got["long cycle"]} == {ERR_ARG}
+    assert [got["two-cycle"][at[(2 + 3 * t, 15)]][0] for t in range(5)] == [OK, ERR_ARG, ERR_ARG, ERR_ARG, ERR_ARG]
+    assert {w[0] for w in got["two-cycle at the root"]} == {ERR_ARG}
+    assert {w[0] for w in got["long cycle with a tail"]} == {ERR_ARG}
+    # pivot 2 labels itself: paths from below it start there, pivots 0 and 1 hang off it too
+    root2 = got["root other than 0"]
+    assert root2[at[(14, 15)]][:2] == (OK, 4) and root2[at[(14, 15)]][3][:2] == [9, 7]
+    assert root2[at[(5, 15)]][:2] == (OK, 4) and root2[at[(5, 15)]][3] == [9, 7, 1, 1, 5, 2, 5, 15]
+    up = got["parent above child"]
+    assert up[at[(8, 15)]][:2] == (OK, 5) and up[at[(8, 15)]][3] == [14, 3, 1, 1, 20, 12, 9, 7, 8, 15]
+    assert up[at[(11, 15)]][:2] == (OK, 2)
+    assert got["two roots"][at[(8, 15)]][:2] == (OK, 4) and got["two roots"][at[(14, 15)]][:2] == (OK, 3)
+    assert {w[0] for w in got["pivot outside the grid at the root"]} == {ERR_ARG}
+    mid = got["pivot outside the grid in mid-chain"]
+    assert [mid[at[(2 + 3 * t, 15)]][0] for t in range(5)] == [OK, OK, ERR_ARG, ERR_ARG, ERR_ARG]
+    assert [got["label of a pivot above n_pivots"][at[(2 + 3 * t, 15)]][0] for t in range(5)] == [OK, OK, ERR_ARG, ERR_ARG, ERR_ARG]
+    assert [w[:2] for w in got["n_pivots = 0"]] == [(OK, 2), (ERR_ARG, 0), (OK, 2), (ERR_ARG, 0)]
+    assert max(w[1] for w in got["longest consistent chain"]) == big + 2
+    assert {w[0] for w in got["longest consistent chain"]} == {OK}
+    assert {w[0] for w in got["longest chain, cap one too small"]} == {OK, ERR_TOO_LARGE}
+
+
+def test_length_is_summed_from_the_start(vhp, drivers):
+    """A chain whose segment lengths add up to a different double from the other end (found by search here): only a running sum from
+    the root -- cum[t] = cum[parent[t]] + eval_d -- matches the host."""
+    rng = np.random.default_rng(5)
+    nx = ny = 200
+    found = None
+    for _ in range(2000):
+        k = int(rng.integers(4, 9))
+        pts = [(int(rng.integers(0, nx)), int(rng.integers(0, ny))) for _ in range(k + 1)]
+        if len(set(pts)) != len(pts):
+            continue
+        seg = [float(np.sqrt(np.float64((a[0] - b[0]) ** 2 + (a[1] - b[1]) ** 2))) for a, b in zip(pts, pts[1:])]
+        fwd = bwd = 0.0
+        for s in seg:
+            fwd += s
+        for s in reversed(seg):
+            bwd += s
+        if fwd != bwd:
+            found = (pts, fwd, bwd)
+            break
+    assert found, "no chain whose two summation orders differ"
+    pts, fwd, bwd = found
+    piv, end = pts[:-1], pts[-1]
+    n = len(piv) - 1
+    came = _table(nx, ny, piv, [max(k - 1, 0) for k in range(n + 1)], [(end[0], end[1], n)])
+    (w,), = _compare(vhp, drivers, [(came, piv, [end], n + 3)])
+    length = struct.unpack("<d", bytes.fromhex(w[2]))[0]
+    assert w[0] == OK and w[1] == len(pts) and w[3] == [v for p in pts for v in p]
+    assert length == fwd and length != bwd

@@ -33,6 +33,8 @@ VHP_ERR_TOO_LARGE = 102
 SWEEP_FULL, SWEEP_QUEUE = 0, 1
 F64, F32 = 0, 1
 UNLABELLED = 1000000000000000
+SOLVE_PLAIN, SOLVE_BATCH, SOLVE_MAPS_BATCH = 0, 1, 2   # vhp_solve_kind: whose tree the length-field and goal-path calls read
+_SOLVE_KINDS = {"plain": SOLVE_PLAIN, "batch": SOLVE_BATCH, "maps": SOLVE_MAPS_BATCH}
 
 # every symbol include/vhp.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = (
@@ -49,6 +51,7 @@ ABI_SYMBOLS = (
     "vhp_planner_solve_maps_batch", "vhp_planner_maps_batch_results_device", "vhp_planner_maps_batch_results", "vhp_planner_maps_batch_group",
     "vhp_planner_batch_paths", "vhp_planner_batch_paths_device", "vhp_planner_maps_batch_paths", "vhp_planner_maps_batch_paths_device",
     "vhp_planner_path", "vhp_planner_path_device",
+    "vhp_planner_length_fields", "vhp_planner_length_fields_device", "vhp_planner_goal_paths", "vhp_planner_goal_paths_device",
 )
 
 
@@ -110,6 +113,10 @@ def load_library():
     for name in ("vhp_planner_batch_paths", "vhp_planner_maps_batch_paths", "vhp_planner_path"):
         getattr(lib, name).argtypes = [vp, vp, u32, vp, vp, vp]
         getattr(lib, name + "_device").argtypes = [vp, vp, u32, vp, vp, vp]
+    for name in ("vhp_planner_length_fields", "vhp_planner_length_fields_device"):
+        getattr(lib, name).argtypes = [vp, i32, i32, i32, vp, vp]
+    for name in ("vhp_planner_goal_paths", "vhp_planner_goal_paths_device"):
+        getattr(lib, name).argtypes = [vp, i32, vp, i32, vp, u32, vp, vp, vp]
     lib.vhp_sweep_batch_variant.argtypes = [vp, vp, i32, f64, f64, vp]
     lib.vhp_planner_solve_variant.argtypes = [vp, i32, i32, i32, i32, f64, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_sweep_batch_offset.argtypes = [vp, vp, i32, f64, vp]
@@ -406,6 +413,50 @@ class Context:
         """vhp_planner_path_device (see planner_batch_paths_device)."""
         self._check(self.lib.vhp_planner_path_device(self.h, C.c_void_p(d_path_xy or None), int(cap), C.c_void_p(d_n_path or None),
                                                      C.c_void_p(d_length or None), C.c_void_p(d_status or None)))
+
+    def _solve_kind(self, solve):
+        """(vhp_solve_kind, queries of that solve, its default path room, nx, ny) for solve = "plain" | "batch" | "maps" (or the constant)"""
+        kind = _SOLVE_KINDS[solve] if isinstance(solve, str) else int(solve)
+        if kind == SOLVE_PLAIN:
+            return kind, 1, self._path_cap, self.nx, self.ny
+        if kind == SOLVE_BATCH:
+            return (kind,) + tuple(self._batch_q) + (self.nx, self.ny)
+        if kind == SOLVE_MAPS_BATCH:
+            return (kind,) + tuple(self._maps_batch_q) + (self.maps_nx, self.maps_ny)
+        raise ValueError("solve must be 'plain', 'batch' or 'maps', got %r" % (solve,))
+
+    def planner_length_fields(self, solve="plain", q_first=0, n_q=None):
+        """vhp_planner_length_fields: for queries q_first .. q_first + n_q - 1 of a solve (default: all from q_first) the path length from
+        the query's start to EVERY cell and that path's point count, read off the tree the solve left on the device.  Returns (length
+        float64 [n_q, ny, nx], n_path uint32 [n_q, ny, nx]); a cell the solve did not reach has length -1.0 and n_path 0."""
+        kind, n, _, nx, ny = self._solve_kind(solve)
+        n_q = n - int(q_first) if n_q is None else int(n_q)
+        length = np.empty((max(n_q, 0), ny, nx), np.float64)
+        cnt = np.empty((max(n_q, 0), ny, nx), np.uint32)
+        self._check(self.lib.vhp_planner_length_fields(self.h, kind, int(q_first), n_q, _ptr(length), _ptr(cnt)))
+        return length, cnt
+
+    def planner_length_fields_device(self, d_length, d_n_path=0, solve="plain", q_first=0, n_q=None):
+        """vhp_planner_length_fields_device: raw device pointers (0: not wanted), asynchronous on the context stream."""
+        kind, n, _, _, _ = self._solve_kind(solve)
+        n_q = n - int(q_first) if n_q is None else int(n_q)
+        self._check(self.lib.vhp_planner_length_fields_device(self.h, kind, int(q_first), n_q, C.c_void_p(d_length or None), C.c_void_p(d_n_path or None)))
+
+    def planner_goal_paths(self, goals, solve="plain", cap=None):
+        """vhp_planner_goal_paths: the path from a query's start to each goal -- goals int32 [n, 3] rows (q, x, y) -- reconstructed on the
+        device.  A list of dict(status, length, n_path, path) as planner_batch_paths gives per query.  cap: points of room per goal
+        (default: the largest n_pivots + 2 of the solve, enough for any cell)."""
+        kind, _, dflt, _, _ = self._solve_kind(solve)
+        g = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+        call = lambda h, xy, cap, cnt, length, st: self.lib.vhp_planner_goal_paths(h, kind, _ptr(g), len(g), xy, cap, cnt, length, st)
+        return self._paths(call, len(g), dflt if cap is None else cap)
+
+    def planner_goal_paths_device(self, d_goals, n_goals, d_path_xy, cap, d_n_path=0, d_length=0, d_status=0, solve="plain"):
+        """vhp_planner_goal_paths_device: raw device pointers (0: not wanted), asynchronous on the context stream."""
+        kind = self._solve_kind(solve)[0]
+        self._check(self.lib.vhp_planner_goal_paths_device(self.h, kind, C.c_void_p(d_goals or None), int(n_goals), C.c_void_p(d_path_xy or None),
+                                                           int(cap), C.c_void_p(d_n_path or None), C.c_void_p(d_length or None),
+                                                           C.c_void_p(d_status or None)))
 
     def _batch_outputs(self, st, npiv, outputs, nx, ny, results):
         n = len(st)

@@ -23,6 +23,7 @@
 #include "vhp_planner.hip.h"
 #include "vhp_planner_batch.hip.h"
 #include "vhp_paths.hip.h"
+#include "vhp_tree.hip.h"
 #include "vhp_queue.hip.h"
 #include "vhp_variant.hip.h"
 #include "vhp_union.hip.h"
@@ -111,6 +112,7 @@ struct vhp_ctx {
                                     // on the stack that takes the latency sweep (vhp_planner_solve_maps_batch), kept until the stack goes
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
+  vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
 };
 
 namespace {
@@ -652,6 +654,70 @@ int plain_path(vhp_ctx* ctx, const char* who, bool device, int32_t* path_xy, uin
   return paths_call(ctx, who, plain_paths_dev(ctx), device, path_xy, cap, n_path, length, path_status);
 }
 
+// The solve a tree call names (vhp_solve_kind), as the path calls see it: the last plain / speculative solve as a batch of one, the
+// last batch, the last maps batch.  The errors are those of the path calls.
+int tree_solve(vhp_ctx* ctx, const char* who, int solve, vhp::PathsDev* p) {
+  if (solve == VHP_SOLVE_PLAIN) {
+    if (ctx->pl.path_state == 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": no planner solve has run on this map");
+    *p = plain_paths_dev(ctx);
+    return VHP_OK;
+  }
+  if (solve != VHP_SOLVE_BATCH && solve != VHP_SOLVE_MAPS_BATCH) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": solve is not a vhp_solve_kind");
+  const bool maps = solve == VHP_SOLVE_MAPS_BATCH;
+  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
+  *p = batch_paths_dev(b, b.codes, maps ? ctx->maps_nx : ctx->nx, maps ? ctx->maps_ny : ctx->ny);
+  return VHP_OK;
+}
+
+int length_fields(vhp_ctx* ctx, const char* who, bool device, int solve, int q_first, int n_q, double* length, uint32_t* n_path) {
+  if (!ctx) return VHP_ERR_ARG;
+  vhp::PathsDev p{};
+  if (int rc = tree_solve(ctx, who, solve, &p); rc != VHP_OK) return rc;
+  if (q_first < 0 || n_q < 1 || q_first > p.n_queries - n_q) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query range outside the solve's queries");
+  if (!length && !n_path) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": both outputs are null");
+  if (device && ((reinterpret_cast<uintptr_t>(length) & 7) || (reinterpret_cast<uintptr_t>(n_path) & 3)))
+    return fail(ctx, VHP_ERR_ARG, std::string(who) + ": an output is not aligned to its element type");
+  VHP_ON_DEVICE(ctx);
+  const hipError_t e = device ? vhp::tree_fields_launch(ctx->tree, p, q_first, n_q, ctx->stream, length, n_path)
+                              : vhp::tree_fields_host(ctx->tree, p, q_first, n_q, ctx->stream, length, n_path);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return VHP_OK;
+}
+
+int goal_paths(vhp_ctx* ctx, const char* who, bool device, int solve, const int32_t* goals, int n_goals, int32_t* path_xy, uint32_t cap,
+               uint32_t* n_path, double* length, int32_t* path_status) {
+  if (!ctx) return VHP_ERR_ARG;
+  vhp::PathsDev p{};
+  if (int rc = tree_solve(ctx, who, solve, &p); rc != VHP_OK) return rc;
+  if (n_goals < 0 || (n_goals > 0 && !goals)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": null goals or a negative count");
+  if (n_goals == 0) return VHP_OK;
+  if (device && ((reinterpret_cast<uintptr_t>(length) & 7) || ((reinterpret_cast<uintptr_t>(goals) | reinterpret_cast<uintptr_t>(path_xy) |
+                                                                 reinterpret_cast<uintptr_t>(n_path) | reinterpret_cast<uintptr_t>(path_status)) & 3)))
+    return fail(ctx, VHP_ERR_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+  if (!device)
+    for (int g = 0; g < n_goals; ++g)
+      if (goals[3 * (size_t)g] < 0 || goals[3 * (size_t)g] >= p.n_queries)
+        return fail(ctx, VHP_ERR_ARG, std::string(who) + ": goal " + std::to_string(g) + " names a query outside the solve's queries");
+  VHP_ON_DEVICE(ctx);
+  hipError_t e;
+  if (device) {
+    vhp::TreeGoalArgs a{};
+    a.goals = goals;
+    a.n_goals = n_goals;
+    a.path_xy = path_xy;
+    a.cap = cap;
+    a.n_path = n_path;
+    a.length = length;
+    a.status = path_status;
+    e = vhp::tree_goals_launch(ctx->tree, p, ctx->stream, a);
+  } else {
+    e = vhp::tree_goals_host(ctx->tree, p, ctx->stream, goals, n_goals, path_xy, cap, n_path, length, path_status);
+  }
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return VHP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -689,6 +755,7 @@ int vhp_destroy(vhp_ctx* ctx) {
   free_map(ctx);
   free_maps(ctx);
   vhp::paths_free(ctx->paths);
+  vhp::tree_free(ctx->tree);
   for (void* p : {(void*)ctx->d_src, (void*)ctx->d_map_idx, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
     if (p) (void)hipFree(p);
   for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1504,6 +1571,21 @@ int vhp_planner_path(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_p
 }
 int vhp_planner_path_device(vhp_ctx* ctx, int32_t* d_path_xy, uint32_t cap, uint32_t* d_n_path, double* d_length, int32_t* d_path_status) {
   return plain_path(ctx, "vhp_planner_path_device", true, d_path_xy, cap, d_n_path, d_length, d_path_status);
+}
+
+int vhp_planner_length_fields(vhp_ctx* ctx, int solve, int q_first, int n_q, double* length, uint32_t* n_path) {
+  return length_fields(ctx, "vhp_planner_length_fields", false, solve, q_first, n_q, length, n_path);
+}
+int vhp_planner_length_fields_device(vhp_ctx* ctx, int solve, int q_first, int n_q, double* d_length, uint32_t* d_n_path) {
+  return length_fields(ctx, "vhp_planner_length_fields_device", true, solve, q_first, n_q, d_length, d_n_path);
+}
+int vhp_planner_goal_paths(vhp_ctx* ctx, int solve, const int32_t* goals_qxy, int n_goals, int32_t* path_xy, uint32_t cap, uint32_t* n_path,
+                           double* length, int32_t* path_status) {
+  return goal_paths(ctx, "vhp_planner_goal_paths", false, solve, goals_qxy, n_goals, path_xy, cap, n_path, length, path_status);
+}
+int vhp_planner_goal_paths_device(vhp_ctx* ctx, int solve, const int32_t* d_goals_qxy, int n_goals, int32_t* d_path_xy, uint32_t cap,
+                                  uint32_t* d_n_path, double* d_length, int32_t* d_path_status) {
+  return goal_paths(ctx, "vhp_planner_goal_paths_device", true, solve, d_goals_qxy, n_goals, d_path_xy, cap, d_n_path, d_length, d_path_status);
 }
 
 // eval_d of visibilityBasedSolver.h:112-115 (host side, used only for the path length)
