@@ -10,8 +10,33 @@ namespace vhp {
 
 struct PlannerDev;  // (vhp_planner_dev.hip.h)
 
+// The packed copies of n maps of one size (vhp_set_map: n = 1; vhp_set_maps: a stack, map k's words k strides after map 0's).
+struct PackedMaps {
+  int n = 0, nx = 0, ny = 0, wpr = 0, wpc = 0;
+  uint64_t* rows = nullptr;   // packed along x: map k's words at rows + k * ny * wpr
+  uint64_t* cols = nullptr;   // packed along y: map k's at cols + k * nx * wpc
+  double* recip = nullptr;    // one reciprocal table for max(nx, ny)
+  uint64_t* dmap = nullptr;   // packed along both diagonals (lat_pack_diag_maps / lat_pack_diag_stack): what the latency sweep reads,
+                              // map k's lat_diag_map_bytes further; null where the latency sweep does not take the grid (or, for a
+                              // stack, until the first planner batch on it builds them)
+};
+
+// What a latency-sweep launch from a planner's loop adds to a plain batch sweep (every member unset: a plain one).
+struct LatLaunch {
+  const int* src_index = nullptr;  // sweep source number *src_index of d_src (n_src = 1) ...
+  const int* skip = nullptr;       // ... and nothing at all if *skip is set
+  const int* pivot_rec = nullptr;  // ... or, instead of both: the 16-byte record {done, nb, x, y} of the planner's loop (LatArgs::pivot_rec)
+  const int* slot_base = nullptr;  // the speculative and the batch planner's launches (LatArgs::slot_base, run_if)
+  const int* run_if = nullptr;
+  bool dark_unwritten = false;     // dead strips store nothing: the field holds +0.0 wherever the launch does not write
+  const PlannerDev* planner_dev = nullptr;  // the launch is a whole planner iteration (launch_lat)
+  // fp64, on a stack of maps (BatchArgs::n_maps of them, rows / cols / dmap those of map 0): field s is swept on map
+  // map_idx[*slot_base + s] (vhp_lat.hip vhp_lat_maps_sweep) -- or null: one map
+  const int32_t* map_idx = nullptr;
+};
+
 struct BatchArgs {
-  const uint64_t* rows;   // packed maps and reciprocal table of the context (vhp_set_map)
+  const uint64_t* rows;   // packed maps and reciprocal table of the context (set_maps below)
   const uint64_t* cols;
   const double* recip;
   const uint64_t* dmap = nullptr;  // the occupancy packed along diagonals (lat_pack_diag_maps): what the latency sweep reads
@@ -39,18 +64,16 @@ struct BatchArgs {
   int pool_early_ctx = 0, pool_late_pct = 0;  // pool sweep: contexts >= early_ctx open once late_pct % of the units are taken (0: all open)
   int pool_busy_cap = 0;  // pool sweep: a workgroup takes another unit only while fewer wavefronts than this are sweeping (0: no cap)
   int pool_static_round = 2;  // pool sweep: every context's first unit by workgroup index, no pull (vhp_pool.hpp Args::static_round; 2: odd head contexts count down, Args::static_snake); 0: every unit pulled
-  const int* d_src_index = nullptr;  // latency sweep in the planner's loop: sweep source number *d_src_index of d_src (n_src = 1) ...
-  const int* d_skip = nullptr;       // ... and nothing at all if *d_skip is set
-  const int* d_pivot_rec = nullptr;  // ... or, instead of both: the 16-byte record {done, nb, x, y} of the planner's loop (LatArgs::pivot_rec)
-  const int* d_slot_base = nullptr;  // the speculative planner's launches (LatArgs::slot_base, run_if)
-  const int* d_run_if = nullptr;
-  bool lat_dead_cells_are_zero = false;  // ... and dead strips store nothing: the field holds +0.0 wherever the launch does not write
+  LatLaunch lat;          // latency sweep: the launch of a planner's loop
   unsigned long long pool_epoch = 0;  // pool sweep: the tag of this launch's boundary-line entries: never 0, never reused on this scratch
-  // latency sweep, fp64: a stack of n_maps maps of this size (vhp_set_maps), rows / cols / dmap those of map 0; field s is swept on map
-  // d_map_idx[*d_slot_base + s] (vhp_lat.hip vhp_lat_maps_sweep) -- or null: one map
-  const int32_t* d_map_idx = nullptr;
-  int n_maps = 0;
+  int n_maps = 0;         // maps behind rows / cols / dmap (PackedMaps::n)
 };
+
+inline void set_maps(BatchArgs& a, const PackedMaps& m) {
+  a.rows = m.rows; a.cols = m.cols; a.recip = m.recip; a.dmap = m.dmap;
+  a.wpr = m.wpr; a.wpc = m.wpc; a.nx = m.nx; a.ny = m.ny;
+  a.n_maps = m.n;
+}
 
 // The pool sweep (vhp_pool.hip): d_queue is scratch of pool_scratch_bytes (pull counter, unit order, the
 // diagonal lines of the y-major units, the boundary lines of the strips) that is ZERO when it is first used and is
@@ -63,10 +86,10 @@ size_t pool_scratch_bytes(int n_src, int nx, int ny);
 // lat_scratch_bytes with the pool sweep's rules (zero when first used, written by nothing but these two kernels; the two
 // share the epoch counter, so either may follow the other on one allocation).
 bool lat_supported(int nx, int ny);
+// With a.lat.planner_dev (d), a planner iteration as one launch: the latency sweep of the pivot named by a.lat.pivot_rec (fp64, into
+// a.d_out) and, in the same grid, the epilogue over d (union, labels, heuristic, next pivot: vhp_planner_dev.hip.h).  d.ticket[1] counts
+// the sweep's workgroups.
 hipError_t launch_lat(const BatchArgs& a);
-// A planner iteration as one launch: the latency sweep of the pivot named by a.d_pivot_rec (fp64, into a.d_out) and, in the same
-// grid, the epilogue over d (union, labels, heuristic, next pivot: vhp_planner_dev.hip.h).  d.ticket[1] counts the sweep's workgroups.
-hipError_t launch_lat_planner(const BatchArgs& a, const PlannerDev& d);
 size_t lat_scratch_bytes(int n_src, int nx, int ny);
 size_t lat_order_bytes();
 // The latency sweep's lanes run along diagonals of the grid: it reads the occupancy packed along them (vhp_band.hpp DiagMaps),

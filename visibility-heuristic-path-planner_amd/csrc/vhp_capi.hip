@@ -42,14 +42,9 @@ struct vhp_ctx {
   double last_alloc_ms = 0.0;  // what the last vhp_alloc_output cost: wall time of the search ...
   unsigned long long last_alloc_peak_bytes = 0;  // ... and the device memory it held at its peak (vhp_alloc_output_cost)
   int opt_alloc_budget_pct = 25;  // vhp_alloc_output: share of the free device memory its candidates may hold at once
-  int nx = 0, ny = 0;
-  uint8_t* d_occ = nullptr;    // uint8 map (kept for the planner's validation and packing)
-  std::vector<uint8_t> h_occ;  // ... its host copy when vhp_set_map brought it (empty after vhp_set_map_device)
-  uint64_t* d_rows = nullptr;  // packed along x
-  uint64_t* d_cols = nullptr;  // packed along y
-  double* d_recip = nullptr;
-  uint64_t* d_dmap = nullptr;  // packed along both diagonals, by x and by y (the latency sweep's maps: vhp_batch_launch.h lat_pack_diag_maps)
-  int wpr = 0, wpc = 0;
+  vhp::PackedMaps map;         // the map of vhp_set_map (n == 1): its packed copies, with the diagonal maps where the latency sweep takes the grid
+  uint8_t* d_occ = nullptr;    // ... its uint8 form (kept for the planner's validation and packing)
+  std::vector<uint8_t> h_occ;  // ... and that one's host copy when vhp_set_map brought it (empty after vhp_set_map_device)
   int* d_err = nullptr;
 
   // grow-only scratch (grow), capacities in bytes; first the host-buffer sweep entry points' (stage_batch)
@@ -77,13 +72,6 @@ struct vhp_ctx {
   int opt_slide = -1;         // 0 / 1: y-major column grid slid onto 128-byte lines
   int opt_pack = 0;           // 1: pack short quadrants into one workgroup
   int opt_lat_workgroups = 0; // latency sweep: workgroups per octant (0 automatic, 1 / 2 / 4 / 8: vhp_lat.hip lat_halves)
-  const int* lat_src_index = nullptr;  // set around a latency-sweep launch of the planner's loop (vhp_planner_solve)
-  const int* lat_skip = nullptr;
-  const int* lat_pivot_rec = nullptr;  // ... or both and the pivot in one 16-byte record (vhp_planner.hip.h PlannerDev::rec)
-  const vhp::PlannerDev* planner_dev = nullptr;  // ... and the launch is a whole planner iteration (vhp_batch_launch.h launch_lat_planner)
-  const int* lat_slot_base = nullptr;  // ... of the speculative planner's (vhp_planner_solve_speculative)
-  const int* lat_run_if = nullptr;
-  bool lat_dark_unwritten = false;
   int opt_kernel = 0;         // 0 auto, 1 front sweep (vhp_sweep_fronts), 3 pool sweep (vhp_pool), 4 latency sweep (vhp_lat); 2 was the streaming sweep (retired in round 4)
   int last_kernel = 0;         // what the last batch sweep launched: 1 front sweep, 3 pool sweep, 4 latency sweep
   long long opt_field_stride = 0;  // device-pointer batch sweeps: elements from one field to the next (0: nx * ny, packed)
@@ -101,15 +89,11 @@ struct vhp_ctx {
   int opt_planner_batch_group = 0;  // queries per group of a batch solve at most (0: automatic, planner_batch_group_size)
   vhp::QueueScratch qs;  // scratch of the queue-variant sweep
 
-  // the stack of maps of vhp_set_maps (vhp_sweep_maps_batch): state of its own, apart from the single map above
-  int maps_n = 0, maps_nx = 0, maps_ny = 0, maps_wpr = 0, maps_wpc = 0;
-  uint64_t* d_maps_rows = nullptr;  // map k's row-packed words at d_maps_rows + k*maps_ny*maps_wpr
-  uint64_t* d_maps_cols = nullptr;  // ... column-packed ones at d_maps_cols + k*maps_nx*maps_wpc
-  double* d_maps_recip = nullptr;   // one reciprocal table for max(maps_nx, maps_ny)
+  // the stack of maps of vhp_set_maps (vhp_sweep_maps_batch): state of its own, apart from the single map above; its diagonal maps are
+  // built by the first planner batch on the stack that takes the latency sweep (vhp_planner_solve_maps_batch) and kept until the stack goes
+  vhp::PackedMaps maps;
   int32_t* d_map_idx = nullptr;     // host-buffer form's slice of map indices (grow)
   size_t d_map_idx_cap = 0;
-  uint64_t* d_maps_dmap = nullptr;  // every map's diagonal maps (map k's k * lat_diag_map_bytes further): built by the first planner batch
-                                    // on the stack that takes the latency sweep (vhp_planner_solve_maps_batch), kept until the stack goes
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
   vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
@@ -161,65 +145,47 @@ int fail(vhp_ctx* c, int code, const std::string& msg) {
   DeviceGuard device_guard_((ctx)->device); \
   if (!device_guard_.ok) return fail((ctx), VHP_ERR_HIP, "hipSetDevice failed")
 
-vhp::DevMap dev_map(const vhp_ctx* c) {
+// Map 0 of p; a sweep on a stack moves to map k by k times maps_stack's strides.
+vhp::DevMap dev_map(const vhp::PackedMaps& p) {
   vhp::DevMap m;
-  m.rows = c->d_rows;
-  m.cols = c->d_cols;
-  m.recip = c->d_recip;
-  m.wpr = c->wpr;
-  m.wpc = c->wpc;
-  m.nx = c->nx;
-  m.ny = c->ny;
+  m.rows = p.rows;
+  m.cols = p.cols;
+  m.recip = p.recip;
+  m.wpr = p.wpr;
+  m.wpc = p.wpc;
+  m.nx = p.nx;
+  m.ny = p.ny;
   m.bnd = nullptr;
   m.bnd_len = 0;
   m.slide = 0;  // set per launch (launch_sweep_t)
   return m;
 }
 
-// Map 0 of the stack of vhp_set_maps; the sweep moves to map k by k times maps_stack's strides.
-vhp::DevMap stack_dev_map(const vhp_ctx* c) {
-  vhp::DevMap m = dev_map(c);
-  m.rows = c->d_maps_rows;
-  m.cols = c->d_maps_cols;
-  m.recip = c->d_maps_recip;
-  m.wpr = c->maps_wpr;
-  m.wpc = c->maps_wpc;
-  m.nx = c->maps_nx;
-  m.ny = c->maps_ny;
-  return m;
+vhp::MapStack maps_stack(const vhp::PackedMaps& p, const int32_t* d_map_idx) {
+  return {d_map_idx, p.n, (long long)p.ny * p.wpr, (long long)p.nx * p.wpc};
 }
 
-vhp::MapStack maps_stack(const vhp_ctx* c, const int32_t* d_map_idx) {
-  return {d_map_idx, c->maps_n, (long long)c->maps_ny * c->maps_wpr, (long long)c->maps_nx * c->maps_wpc};
+void free_packed(vhp::PackedMaps& p) {
+  for (void* q : {(void*)p.rows, (void*)p.cols, (void*)p.recip, (void*)p.dmap})
+    if (q) (void)hipFree(q);
+  p = vhp::PackedMaps{};
 }
-
-}  // namespace
-
-namespace {
 
 void free_map(vhp_ctx* c) {
   if (c->d_occ) hipFree(c->d_occ);
-  if (c->d_rows) hipFree(c->d_rows);
-  if (c->d_cols) hipFree(c->d_cols);
-  if (c->d_recip) hipFree(c->d_recip);
-  if (c->d_dmap) hipFree(c->d_dmap);
-  c->d_occ = nullptr; c->d_rows = nullptr; c->d_cols = nullptr; c->d_recip = nullptr; c->d_dmap = nullptr;
+  c->d_occ = nullptr;
+  free_packed(c->map);
   c->h_occ.clear();
   c->pl.h_occ = nullptr;
   vhp::planner_free(c->pl);
   vhp::spec_free(c->spec);
   vhp::batch_free(c->batch);
   vhp::queue_scratch_free(c->qs);
-  c->nx = c->ny = 0;
 }
 
 void free_maps(vhp_ctx* c) {
-  for (void* p : {(void*)c->d_maps_rows, (void*)c->d_maps_cols, (void*)c->d_maps_recip, (void*)c->d_maps_dmap})
-    if (p) (void)hipFree(p);
+  free_packed(c->maps);
   vhp::batch_free(c->maps_batch);
-  c->d_maps_rows = c->d_maps_cols = c->d_maps_dmap = nullptr;
-  c->d_maps_recip = nullptr;
-  c->maps_n = c->maps_nx = c->maps_ny = c->maps_wpr = c->maps_wpc = 0;
 }
 
 // RN(1/k) for k = 1 .. max(nx, ny) + kRecipPad, and 0 for k = 0
@@ -247,11 +213,19 @@ hipError_t grow(T** p, size_t* cap_bytes, size_t bytes, bool zero, hipStream_t s
   return e;
 }
 
-// A launch's timing events while vhp_timing is on (else none): a recycled pair, or a new one.
+// How an internal launch writes its fields and whether vhp_timing times it.  The entry point passes it down; nothing parks it on the
+// context around a call.  The default is the planner loops': packed fields, and no per-launch event pairs (vhp_timing times sweep
+// launches, and a loop enqueues launches past its end that return at once -- they would fill the pool with pairs that time nothing).
+struct LaunchOpts {
+  long long field_stride = 0;  // elements from one field to the next (0: nx * ny, packed)
+  bool timed = false;
+};
+
+// A timed launch's events (else none): a recycled pair, or a new one.
 using EventPair = std::pair<hipEvent_t, hipEvent_t>;
-hipError_t acquire_events(vhp_ctx* c, EventPair* ev) {
+hipError_t acquire_events(vhp_ctx* c, bool timed, EventPair* ev) {
   *ev = {nullptr, nullptr};
-  if (!c->timing) return hipSuccess;
+  if (!timed) return hipSuccess;
   if (!c->event_pool.empty()) { *ev = c->event_pool.back(); c->event_pool.pop_back(); return hipSuccess; }
   if (hipEventCreate(&ev->first) != hipSuccess) return hipErrorOutOfMemory;
   if (hipEventCreate(&ev->second) == hipSuccess) return hipSuccess;
@@ -263,22 +237,17 @@ void release_events(vhp_ctx* c, const EventPair& ev, hipError_t launched) {
   if (ev.first) (launched == hipSuccess ? c->timed_launches : c->event_pool).push_back(ev);
 }
 
-// The front sweep's shape for a batch of n_src sources on the stack of maps: the same plan with the kernel forced to 1.
-vhp::SweepPlan plan_for_maps(const vhp_ctx* c, int n_src, bool f64) {
-  return vhp::plan_sweep({c->maps_nx, c->maps_ny, n_src, c->n_cus, f64,
-                          {1, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, false, false, false});
+// What sweeps a batch of n_src sources on m's grid with the context's options (vhp_choice.hpp), or with `kernel` in place of the option.
+vhp::SweepPlan plan_for_grid(const vhp_ctx* c, const vhp::PackedMaps& m, int n_src, bool f64, int kernel = 0) {
+  const bool lat_ok = vhp::lat_supported(m.nx, m.ny);
+  return vhp::plan_sweep({m.nx, m.ny, n_src, c->n_cus, f64,
+                          {kernel ? kernel : c->opt_kernel, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, lat_ok,
+                          vhp::pool_supported(m.nx, m.ny), lat_ok && vhp::lat_scratch_bytes(n_src, m.nx, m.ny) <= ((size_t)2 << 30)});
 }
 
-// What sweeps a batch of n_src sources on an nx x ny grid with the context's options (vhp_choice.hpp).
-vhp::SweepPlan plan_for_grid(const vhp_ctx* c, int nx, int ny, int n_src, bool f64) {
-  const bool lat_ok = vhp::lat_supported(nx, ny);
-  return vhp::plan_sweep({nx, ny, n_src, c->n_cus, f64,
-                          {c->opt_kernel, c->opt_rows_per_lane, c->opt_strips, c->opt_multi, c->opt_slide, c->opt_pack}, lat_ok,
-                          vhp::pool_supported(nx, ny), lat_ok && vhp::lat_scratch_bytes(n_src, nx, ny) <= ((size_t)2 << 30)});
-}
-
-// ... on the context's grid
-vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) { return plan_for_grid(c, c->nx, c->ny, n_src, f64); }
+// ... on the context's map, and on its stack of maps: always the front sweep there (vhp_sweep_fronts_maps)
+vhp::SweepPlan plan_for(const vhp_ctx* c, int n_src, bool f64) { return plan_for_grid(c, c->map, n_src, f64); }
+vhp::SweepPlan plan_for_maps(const vhp_ctx* c, int n_src, bool f64) { return plan_for_grid(c, c->maps, n_src, f64, 1); }
 
 // The planner's sweeps of n_src sources: the plan, and the front sweep's shape and round scratch (n_workgroups) from it.
 hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workgroups, vhp::SweepPlan* plan) {
@@ -294,10 +263,10 @@ hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workg
 }
 
 // The front sweep: a workgroup sweeps one quadrant with 2*W wavefronts (W strips per octant) and R rows/columns per lane;
-// fronts longer than W*64*R are swept in rounds (MULTI).  With `stack`, on the stack of maps (vhp_sweep_fronts_maps).
+// fronts longer than W*64*R are swept in rounds (MULTI).  With `stack`, pm is a stack of maps (vhp_sweep_fronts_maps).
 template <int R, bool MULTI, typename OutT>
-hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& plan,
-                          const vhp::MapStack* stack = nullptr) {
+hipError_t launch_sweep_t(vhp_ctx* c, const vhp::PackedMaps& pm, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& plan,
+                          const LaunchOpts& o, const vhp::MapStack* stack) {
   const int W = plan.W;
   const bool pack = c->opt_pack != 0;
   const size_t lds = vhp::sweep_lds_bytes(R, W, MULTI, pack);
@@ -307,8 +276,8 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
     hipError_t e = raise_lds_limit(c, stack ? reinterpret_cast<const void*>(km) : reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return e;
   }
-  vhp::DevMap m = stack ? stack_dev_map(c) : dev_map(c);
-  const long long stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)m.nx * m.ny;
+  vhp::DevMap m = dev_map(pm);
+  const long long stride = o.field_stride > 0 ? o.field_stride : (long long)m.nx * m.ny;
   m.slide = plan.slide;
   hipError_t eb = vhp::attach_round_scratch(m, W * 64 * R, (size_t)n_src * vhp::kUnitsPerSource, &c->d_bnd, &c->d_bnd_cap);
   if (eb != hipSuccess) return eb;
@@ -317,7 +286,7 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
   const int4* desc = nullptr;
   // per-launch timing: from before the unit-ordering pre-kernel (part of what a launch costs) to after the sweep
   EventPair ev;
-  if (hipError_t ee = acquire_events(c, &ev); ee != hipSuccess) return ee;
+  if (hipError_t ee = acquire_events(c, o.timed, &ev); ee != hipSuccess) return ee;
   if (ev.first) (void)hipEventRecord(ev.first, c->stream);
   if (n_src >= 8) {  // worth a 1-workgroup pre-kernel once the batch spans many CUs
     hipError_t eo = grow(&c->d_order, &c->d_order_cap, n_units * (sizeof(int) + sizeof(int4)) + 16, false, c->stream);
@@ -341,37 +310,23 @@ hipError_t launch_sweep_t(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_o
   return el;
 }
 
-// The pool sweep (lat = false) or the latency sweep (lat = true), through vhp_batch_launch.h.  With d_map_idx: the latency sweep on the
-// stack of maps, source s on map d_map_idx[s] (its diagonal maps built: d_maps_dmap).
+// The pool sweep (lat = false) or the latency sweep (lat = true) on m, through vhp_batch_launch.h.  l: what a planner's loop adds to a
+// latency sweep; with l.map_idx, m is the stack of maps and source s is swept on map l.map_idx[s] (its diagonal maps built: m.dmap).
 template <typename OutT>
-hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, bool lat, const int32_t* d_map_idx = nullptr) {
-  const bool on_stack = d_map_idx != nullptr;
-  const int nx = on_stack ? c->maps_nx : c->nx, ny = on_stack ? c->maps_ny : c->ny;
+hipError_t launch_batch_sweep(vhp_ctx* c, const vhp::PackedMaps& m, const int32_t* d_src, int n_src, OutT* d_out, bool lat, const LaunchOpts& o,
+                              const vhp::LatLaunch& l = {}) {
   // (the scratch is an allocation of its own: nothing but these two kernels may write the tagged lines)
-  const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, nx, ny) : vhp::pool_scratch_bytes(n_src, nx, ny);
+  const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, m.nx, m.ny) : vhp::pool_scratch_bytes(n_src, m.nx, m.ny);
   if (hipError_t eo = grow(&c->d_pool, &c->d_pool_cap, scratch, true, c->stream); eo != hipSuccess) return eo;
   vhp::BatchArgs a;
-  if (on_stack) {
-    a.rows = c->d_maps_rows; a.cols = c->d_maps_cols; a.recip = c->d_maps_recip; a.dmap = c->d_maps_dmap;
-    a.wpr = c->maps_wpr; a.wpc = c->maps_wpc; a.nx = nx; a.ny = ny;
-    a.d_map_idx = d_map_idx;
-    a.n_maps = c->maps_n;
-  } else {
-    a.rows = c->d_rows; a.cols = c->d_cols; a.recip = c->d_recip; a.dmap = c->d_dmap;
-    a.wpr = c->wpr; a.wpc = c->wpc; a.nx = c->nx; a.ny = c->ny;
-  }
+  vhp::set_maps(a, m);
   a.d_src = d_src; a.n_src = n_src; a.d_out = d_out;
   a.dtype = sizeof(OutT) == 8 ? VHP_F64 : VHP_F32;
-  a.field_stride = c->opt_field_stride > 0 ? c->opt_field_stride : (long long)nx * ny;
+  a.field_stride = o.field_stride > 0 ? o.field_stride : (long long)m.nx * m.ny;
   a.d_err = c->d_err;
   a.d_queue = c->d_pool;
   a.pool_epoch = ++c->pool_epoch;
-  a.d_src_index = lat ? c->lat_src_index : nullptr;
-  a.d_skip = lat ? c->lat_skip : nullptr;
-  a.d_pivot_rec = lat ? c->lat_pivot_rec : nullptr;
-  a.d_slot_base = lat ? c->lat_slot_base : nullptr;
-  a.d_run_if = lat ? c->lat_run_if : nullptr;
-  a.lat_dead_cells_are_zero = lat && c->lat_dark_unwritten;
+  a.lat = l;
   a.lat_workgroups = c->opt_lat_workgroups;
   if (lat)
     if (hipError_t eo = grow(&c->d_lat_order, &c->d_lat_order_cap, vhp::lat_order_bytes(), false, c->stream); eo != hipSuccess) return eo;
@@ -388,43 +343,40 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT*
   a.pool_heads = c->opt_pool_heads;
   a.pool_static_round = c->opt_pool_static_round;
   EventPair ev;
-  if (hipError_t ee = acquire_events(c, &ev); ee != hipSuccess) return ee;
+  if (hipError_t ee = acquire_events(c, o.timed, &ev); ee != hipSuccess) return ee;
   a.ev_begin = ev.first;
   a.ev_end = ev.second;
-  const hipError_t e = lat ? (c->planner_dev ? vhp::launch_lat_planner(a, *c->planner_dev) : vhp::launch_lat(a)) : vhp::launch_pool(a);
+  const hipError_t e = lat ? vhp::launch_lat(a) : vhp::launch_pool(a);
   release_events(c, ev, e);
   return e;
 }
 
-// The front sweep in the build of plan p's shape.
+// The front sweep on pm in the build of plan p's shape.
 template <typename OutT>
-hipError_t launch_fronts(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& p, const vhp::MapStack* st = nullptr) {
-  if constexpr (sizeof(OutT) == 4) {  // (fp32 fields: only the one-row-per-lane builds exist, and the plan asks for no other)
-    return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p, st);
-  } else {
-    switch (p.R) {
-      case 1: return p.multi ? launch_sweep_t<1, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<1, false, OutT>(c, d_src, n_src, d_out, p, st);
-      case 2: return p.multi ? launch_sweep_t<2, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<2, false, OutT>(c, d_src, n_src, d_out, p, st);
-      default: return p.multi ? launch_sweep_t<4, true, OutT>(c, d_src, n_src, d_out, p, st) : launch_sweep_t<4, false, OutT>(c, d_src, n_src, d_out, p, st);
-    }
-  }
+hipError_t launch_fronts(vhp_ctx* c, const vhp::PackedMaps& pm, const int32_t* d_src, int n_src, OutT* d_out, const vhp::SweepPlan& p,
+                         const LaunchOpts& o, const vhp::MapStack* st = nullptr) {
+  // (fp32 fields: only the one-row-per-lane builds exist, and the plan asks for no other)
+  return vhp::with_sweep_shape(sizeof(OutT) == 4 ? 1 : p.R, p.multi, [&](auto r, auto mr) {
+    if constexpr (sizeof(OutT) == 4 && r() != 1) return hipErrorInvalidValue;
+    else return launch_sweep_t<r(), mr(), OutT>(c, pm, d_src, n_src, d_out, p, o, st);
+  });
 }
 
 template <typename OutT>
-hipError_t launch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out) {
+hipError_t launch_sweep(vhp_ctx* c, const int32_t* d_src, int n_src, OutT* d_out, const LaunchOpts& o) {
   const vhp::SweepPlan p = plan_for(c, n_src, sizeof(OutT) == 8);
   c->last_kernel = p.kernel;
-  if (p.kernel != 1) return launch_batch_sweep<OutT>(c, d_src, n_src, d_out, p.kernel == 4);
-  return launch_fronts<OutT>(c, d_src, n_src, d_out, p);
+  if (p.kernel != 1) return launch_batch_sweep<OutT>(c, c->map, d_src, n_src, d_out, p.kernel == 4, o);
+  return launch_fronts<OutT>(c, c->map, d_src, n_src, d_out, p, o);
 }
 
 // A batch on the stack of maps: always the front sweep (vhp_sweep_fronts_maps), in plan_for_maps's shape.
 template <typename OutT>
-hipError_t launch_maps_sweep(vhp_ctx* c, const int32_t* d_src, const int32_t* d_map_idx, int n_src, OutT* d_out) {
+hipError_t launch_maps_sweep(vhp_ctx* c, const int32_t* d_src, const int32_t* d_map_idx, int n_src, OutT* d_out, const LaunchOpts& o) {
   const vhp::SweepPlan p = plan_for_maps(c, n_src, sizeof(OutT) == 8);
   c->last_kernel = 1;
-  const vhp::MapStack st = maps_stack(c, d_map_idx);
-  return launch_fronts<OutT>(c, d_src, n_src, d_out, p, &st);
+  const vhp::MapStack st = maps_stack(c->maps, d_map_idx);
+  return launch_fronts<OutT>(c, c->maps, d_src, n_src, d_out, p, o, &st);
 }
 
 // The host-buffer sweeps: the sources checked on the host, then slices of at most ~1 GiB of output through the context's
@@ -435,9 +387,9 @@ int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src
 template <typename Launch>
 int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t esz, void* out_host, Launch launch) {
   for (int s = 0; s < n_src; ++s)
-    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->nx || src_xy[2 * s + 1] >= ctx->ny)
+    if (src_xy[2 * s] < 0 || src_xy[2 * s + 1] < 0 || src_xy[2 * s] >= ctx->map.nx || src_xy[2 * s + 1] >= ctx->map.ny)
       return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
-  return stage_slices(ctx, who, src_xy, n_src, (size_t)ctx->nx * ctx->ny * esz, out_host, [&](int, int n) { return launch(n); });
+  return stage_slices(ctx, who, src_xy, n_src, (size_t)ctx->map.nx * ctx->map.ny * esz, out_host, [&](int, int n) { return launch(n); });
 }
 
 // ... the slices of fields of `field` bytes: launch(s0, n) sweeps sources s0 .. s0+n-1, staged at d_src
@@ -460,45 +412,46 @@ int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src
   return VHP_OK;
 }
 
-int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
-  // packed copies + reciprocal table
-  ctx->wpr = (nx + 63) / 64 + 2;
-  ctx->wpc = (ny + 63) / 64 + 2;
-  const size_t rows_words = (size_t)ny * ctx->wpr, cols_words = (size_t)nx * ctx->wpc;
-  VHP_HIP(hipMalloc(&ctx->d_rows, rows_words * 8));
-  VHP_HIP(hipMalloc(&ctx->d_cols, cols_words * 8));
-  VHP_HIP(hipMemsetAsync(ctx->d_rows, 0, rows_words * 8, ctx->stream));
-  VHP_HIP(hipMemsetAsync(ctx->d_cols, 0, cols_words * 8, ctx->stream));
-  {
-    const long long waves = (long long)(ctx->wpr - 2) * ny;
-    const int blocks = (int)((waves * 64 + 255) / 256);
-    hipLaunchKernelGGL(vhp::vhp_pack_rows, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_occ, ctx->d_rows, nx, ny, ctx->wpr);
-    VHP_HIP(hipGetLastError());
-  }
-  {
-    const long long waves = (long long)(ctx->wpc - 2) * nx;
-    const int blocks = (int)((waves * 64 + 255) / 256);
-    hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_occ, ctx->d_cols, nx, ny, ctx->wpc);
-    VHP_HIP(hipGetLastError());
-  }
+// The packed copies of n maps of nx x ny into m: allocated and zeroed, packed by pack(wpr, wpc, row_blocks, col_blocks) -- the caller's
+// kernels on the context's stream, blocks of 256 threads for one map's words --, the reciprocal table uploaded, and the sizes recorded
+// once all of it is on the device.  On failure the caller frees what was built.
+template <typename Pack>
+int build_packed(vhp_ctx* ctx, vhp::PackedMaps& m, int n, int nx, int ny, Pack pack) {
+  const int wpr = (nx + 63) / 64 + 2, wpc = (ny + 63) / 64 + 2;
+  const size_t rows_words = (size_t)n * ny * wpr, cols_words = (size_t)n * nx * wpc;
+  VHP_HIP(hipMalloc(&m.rows, rows_words * 8));
+  VHP_HIP(hipMalloc(&m.cols, cols_words * 8));
+  VHP_HIP(hipMemsetAsync(m.rows, 0, rows_words * 8, ctx->stream));
+  VHP_HIP(hipMemsetAsync(m.cols, 0, cols_words * 8, ctx->stream));
+  const unsigned row_blocks = (unsigned)(((long long)(wpr - 2) * ny * 64 + 255) / 256), col_blocks = (unsigned)(((long long)(wpc - 2) * nx * 64 + 255) / 256);
+  if (const int rc = pack(wpr, wpc, row_blocks, col_blocks); rc != VHP_OK) return rc;
   const std::vector<double> recip = recip_table(nx, ny);
-  const int nrec = (int)recip.size();
-  if (vhp::lat_supported(nx, ny)) {
-    const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
-    VHP_HIP(hipMalloc(&ctx->d_dmap, bytes));
-    VHP_HIP(hipMemsetAsync(ctx->d_dmap, 0, bytes, ctx->stream));
-    VHP_HIP(vhp::lat_pack_diag_maps(ctx->d_occ, nx, ny, ctx->d_dmap, ctx->stream));
-  }
-  VHP_HIP(hipMalloc(&ctx->d_recip, nrec * sizeof(double)));
-  VHP_HIP(hipMemcpyAsync(ctx->d_recip, recip.data(), nrec * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(hipMalloc(&m.recip, recip.size() * sizeof(double)));
+  VHP_HIP(hipMemcpyAsync(m.recip, recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   VHP_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->nx = nx;
-  ctx->ny = ny;
+  m.n = n; m.nx = nx; m.ny = ny; m.wpr = wpr; m.wpc = wpc;
   return VHP_OK;
 }
 
-// The stack of vhp_set_maps from the n_maps uint8 maps at src (host or device): both packed copies of every map, one launch
-// each, and the reciprocal table.  On failure the caller frees what was built.
+// The single map from d_occ, with its diagonal maps where the latency sweep takes the grid.
+int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
+  vhp::PackedMaps& m = ctx->map;
+  return build_packed(ctx, m, 1, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
+    hipLaunchKernelGGL(vhp::vhp_pack_rows, dim3(row_blocks), dim3(256), 0, ctx->stream, ctx->d_occ, m.rows, nx, ny, wpr);
+    VHP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(col_blocks), dim3(256), 0, ctx->stream, ctx->d_occ, m.cols, nx, ny, wpc);
+    VHP_HIP(hipGetLastError());
+    if (vhp::lat_supported(nx, ny)) {
+      const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
+      VHP_HIP(hipMalloc(&m.dmap, bytes));
+      VHP_HIP(hipMemsetAsync(m.dmap, 0, bytes, ctx->stream));
+      VHP_HIP(vhp::lat_pack_diag_maps(ctx->d_occ, nx, ny, m.dmap, ctx->stream));
+    }
+    return VHP_OK;
+  });
+}
+
+// The stack of vhp_set_maps from the n_maps uint8 maps at src (host or device): both packed copies of every map, one launch each.
 int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, bool from_device) {
   struct Staged { uint8_t* p = nullptr; ~Staged() { if (p) (void)hipFree(p); } } staged;  // the host maps' device copy, for the packing only
   const size_t cells = (size_t)n_maps * nx * ny;
@@ -508,49 +461,29 @@ int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, boo
     VHP_HIP(hipMemcpyAsync(staged.p, src, cells, hipMemcpyHostToDevice, ctx->stream));
     d_occ = staged.p;
   }
-  const int wpr = (nx + 63) / 64 + 2, wpc = (ny + 63) / 64 + 2;
-  const size_t rows_words = (size_t)n_maps * ny * wpr, cols_words = (size_t)n_maps * nx * wpc;
-  VHP_HIP(hipMalloc(&ctx->d_maps_rows, rows_words * 8));
-  VHP_HIP(hipMalloc(&ctx->d_maps_cols, cols_words * 8));
-  VHP_HIP(hipMemsetAsync(ctx->d_maps_rows, 0, rows_words * 8, ctx->stream));
-  VHP_HIP(hipMemsetAsync(ctx->d_maps_cols, 0, cols_words * 8, ctx->stream));
-  const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernels step through more maps than that)
-  {
-    const long long waves = (long long)(wpr - 2) * ny;
-    const unsigned blocks = (unsigned)((waves * 64 + 255) / 256);
-    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(blocks, gy), dim3(256), 0, ctx->stream, d_occ, ctx->d_maps_rows, n_maps, nx, ny, wpr);
+  vhp::PackedMaps& m = ctx->maps;
+  return build_packed(ctx, m, n_maps, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
+    const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernels step through more maps than that)
+    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.rows, n_maps, nx, ny, wpr);
     VHP_HIP(hipGetLastError());
-  }
-  {
-    const long long waves = (long long)(wpc - 2) * nx;
-    const unsigned blocks = (unsigned)((waves * 64 + 255) / 256);
-    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(blocks, gy), dim3(256), 0, ctx->stream, d_occ, ctx->d_maps_cols, n_maps, nx, ny, wpc);
+    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.cols, n_maps, nx, ny, wpc);
     VHP_HIP(hipGetLastError());
-  }
-  const std::vector<double> recip = recip_table(nx, ny);
-  VHP_HIP(hipMalloc(&ctx->d_maps_recip, recip.size() * sizeof(double)));
-  VHP_HIP(hipMemcpyAsync(ctx->d_maps_recip, recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VHP_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->maps_n = n_maps;
-  ctx->maps_nx = nx;
-  ctx->maps_ny = ny;
-  ctx->maps_wpr = wpr;
-  ctx->maps_wpc = wpc;
-  return VHP_OK;
+    return VHP_OK;
+  });
 }
 
 // G of a batch solve (vhp_planner_solve_batch): the largest of 32, 16, 8, 4, 2 for which a launch of G sources takes the latency sweep
 // and G queries' state fits in a quarter of the free device memory, else 1 -- capped by "planner_batch_group" --; 0 where even one
 // source does not take the latency sweep (the queries then run one by one on the front sweep).
 // (On the stack of maps: the same rule on the stack's nx x ny.)
-int planner_batch_group_size(const vhp_ctx* c, int nx, int ny, uint64_t max_iter) {
-  if (plan_for_grid(c, nx, ny, 1, true).kernel != 4) return 0;
+int planner_batch_group_size(const vhp_ctx* c, const vhp::PackedMaps& m, uint64_t max_iter) {
+  if (plan_for_grid(c, m, 1, true).kernel != 4) return 0;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-  const size_t per_query = vhp::kBatchBytesPerCell * (size_t)nx * ny + 2 * (size_t)(max_iter + 2) * sizeof(int32_t);
+  const size_t per_query = vhp::kBatchBytesPerCell * (size_t)m.nx * m.ny + 2 * (size_t)(max_iter + 2) * sizeof(int32_t);
   int g = 1;
   for (int G = vhp::kBatchMaxGroup; G > 1; G /= 2)
-    if (plan_for_grid(c, nx, ny, G, true).kernel == 4 && (size_t)G * per_query <= free_b / 4) { g = G; break; }
+    if (plan_for_grid(c, m, G, true).kernel == 4 && (size_t)G * per_query <= free_b / 4) { g = G; break; }
   return c->opt_planner_batch_group > 0 ? std::min(g, c->opt_planner_batch_group) : g;
 }
 
@@ -565,10 +498,22 @@ hipError_t launch_batch_fronts(vhp_ctx* c, const vhp::DevMap& m, const vhp::Plan
   return hipGetLastError();
 }
 
-// The last batch's slot of query q, or an error for the _results entry points (of the maps batch with `maps`).
-int batch_slot(vhp_ctx* ctx, const char* who, int q, int* slot, bool maps = false) {
-  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
-  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
+// The batch planner's state on the single map, or with `maps` on the stack: its queries, its maps, and what a call that finds no
+// solved batch there says after its name.
+struct BatchOn {
+  vhp::BatchState& b;
+  vhp::PackedMaps& m;
+  const char* none_solved;
+};
+BatchOn batch_on(vhp_ctx* ctx, bool maps) {
+  if (maps) return {ctx->maps_batch, ctx->maps, ": no maps batch solved on this stack"};
+  return {ctx->batch, ctx->map, ": no batch solved on this map"};
+}
+
+// The last batch's slot of query q, or an error for the _results entry points.
+int batch_slot(vhp_ctx* ctx, const char* who, bool maps, int q, int* slot) {
+  const auto [b, m, none_solved] = batch_on(ctx, maps);
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + none_solved);
   if (q < 0 || q >= (int)b.slot_of.size()) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query index out of range");
   if (b.slot_of[q] < 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": query " + std::to_string(q) + " failed validation and has no results");
   *slot = b.slot_of[q];
@@ -612,8 +557,8 @@ vhp::PathsDev plain_paths_dev(const vhp_ctx* ctx) {
   p.query = nullptr;
   p.end_x = s.last_end_x;
   p.end_y = s.last_end_y;
-  p.nx = ctx->nx;
-  p.ny = ctx->ny;
+  p.nx = ctx->map.nx;
+  p.ny = ctx->map.ny;
   p.n_queries = 1;
   p.slot[0] = (int16_t)(s.path_state == 1 ? 0 : -s.last_code);
   p.nb[0] = s.path_state == 1 ? s.last_nb : 0u;
@@ -642,10 +587,9 @@ int paths_call(vhp_ctx* ctx, const char* who, vhp::PathsDev p, bool device, int3
 int batch_paths(vhp_ctx* ctx, const char* who, bool maps, bool device, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length,
                 int32_t* path_status) {
   if (!ctx) return VHP_ERR_ARG;
-  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
-  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
-  return paths_call(ctx, who, batch_paths_dev(b, b.codes, maps ? ctx->maps_nx : ctx->nx, maps ? ctx->maps_ny : ctx->ny), device, path_xy, cap,
-                    n_path, length, path_status);
+  const auto [b, m, none_solved] = batch_on(ctx, maps);
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + none_solved);
+  return paths_call(ctx, who, batch_paths_dev(b, b.codes, m.nx, m.ny), device, path_xy, cap, n_path, length, path_status);
 }
 
 int plain_path(vhp_ctx* ctx, const char* who, bool device, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {
@@ -663,10 +607,9 @@ int tree_solve(vhp_ctx* ctx, const char* who, int solve, vhp::PathsDev* p) {
     return VHP_OK;
   }
   if (solve != VHP_SOLVE_BATCH && solve != VHP_SOLVE_MAPS_BATCH) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": solve is not a vhp_solve_kind");
-  const bool maps = solve == VHP_SOLVE_MAPS_BATCH;
-  const vhp::BatchState& b = maps ? ctx->maps_batch : ctx->batch;
-  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + (maps ? ": no maps batch solved on this stack" : ": no batch solved on this map"));
-  *p = batch_paths_dev(b, b.codes, maps ? ctx->maps_nx : ctx->nx, maps ? ctx->maps_ny : ctx->ny);
+  const auto [b, m, none_solved] = batch_on(ctx, solve == VHP_SOLVE_MAPS_BATCH);
+  if (!b.solved) return fail(ctx, VHP_ERR_ARG, std::string(who) + none_solved);
+  *p = batch_paths_dev(b, b.codes, m.nx, m.ny);
   return VHP_OK;
 }
 
@@ -793,7 +736,6 @@ static int set_map_common(vhp_ctx* ctx, const uint8_t* src, int nx, int ny, bool
   const int rc = finish_set_map(ctx, nx, ny);
   if (rc != VHP_OK) {  // (nothing half-set: neither the old grid's sides with the new grid's arrays nor a host copy of a map that is not there)
     free_map(ctx);
-    ctx->nx = ctx->ny = 0;
     return rc;
   }
   if (!from_device) ctx->h_occ.assign(src, src + n);
@@ -804,32 +746,37 @@ static int set_map_common(vhp_ctx* ctx, const uint8_t* src, int nx, int ny, bool
 int vhp_set_map(vhp_ctx* ctx, const uint8_t* occ, int nx, int ny) { return set_map_common(ctx, occ, nx, ny, false); }
 int vhp_set_map_device(vhp_ctx* ctx, const uint8_t* d_occ, int nx, int ny) { return set_map_common(ctx, d_occ, nx, ny, true); }
 
-int vhp_sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int variant, int dtype, void* d_out) {
+// vhp_sweep_batch_device writing its fields o.field_stride apart (the entry point: the option; the host-buffer form: packed)
+static int sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int variant, int dtype, void* d_out, const LaunchOpts& o) {
   if (!ctx || !d_src_xy || !d_out || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: bad argument");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_device: no map set");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_device: no map set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   if (variant != VHP_SWEEP_FULL && variant != VHP_SWEEP_QUEUE) return fail(ctx, VHP_ERR_ARG, "bad variant");
   // (any alignment of whole elements is swept -- the kernels' builds for fields off the 16-byte grid --, a pointer inside an element is not)
   if (reinterpret_cast<uintptr_t>(d_out) % (dtype == VHP_F64 ? 8 : 4) != 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: d_out is not aligned to its element type");
-  if (ctx->opt_field_stride > 0 && ctx->opt_field_stride < (long long)ctx->nx * ctx->ny)
+  if (o.field_stride > 0 && o.field_stride < (long long)ctx->map.nx * ctx->map.ny)
     return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: field_stride is smaller than a field (nx * ny elements): the fields would overlap");
-  if (variant == VHP_SWEEP_QUEUE && ctx->opt_field_stride > 0 && ctx->opt_field_stride != (long long)ctx->nx * ctx->ny)
+  if (variant == VHP_SWEEP_QUEUE && o.field_stride > 0 && o.field_stride != (long long)ctx->map.nx * ctx->map.ny)
     return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: the queue variant writes packed fields (field_stride must be 0)");
   if (n_src == 0) return VHP_OK;
   VHP_ON_DEVICE(ctx);
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   hipError_t e;
   if (variant == VHP_SWEEP_QUEUE) {
-    e = vhp::launch_queue_sweep_impl(ctx->qs, dev_map(ctx), ctx->d_occ, d_src_xy, n_src, dtype, d_out, ctx->d_err, ctx->stream);
+    e = vhp::launch_queue_sweep_impl(ctx->qs, dev_map(ctx->map), ctx->d_occ, d_src_xy, n_src, dtype, d_out, ctx->d_err, ctx->stream);
   } else if (dtype == VHP_F64) {
-    e = launch_sweep<double>(ctx, d_src_xy, n_src, static_cast<double*>(d_out));
+    e = launch_sweep<double>(ctx, d_src_xy, n_src, static_cast<double*>(d_out), o);
   } else {
-    e = launch_sweep<float>(ctx, d_src_xy, n_src, static_cast<float*>(d_out));
+    e = launch_sweep<float>(ctx, d_src_xy, n_src, static_cast<float*>(d_out), o);
   }
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(e));
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
   return VHP_OK;
+}
+
+int vhp_sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int variant, int dtype, void* d_out) {
+  return sweep_batch_device(ctx, d_src_xy, n_src, variant, dtype, d_out, {ctx ? ctx->opt_field_stride : 0, ctx && ctx->timing});
 }
 
 int vhp_sync(vhp_ctx* ctx) {
@@ -847,13 +794,11 @@ int vhp_sync(vhp_ctx* ctx) {
 
 int vhp_sweep_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int variant, int dtype, void* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch: bad argument");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch: no map set");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch: no map set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   // (the library's own scratch holds packed fields and is copied out packed: "field_stride" is a property of a caller's device buffer)
-  struct PackedHere { long long& v; long long keep; ~PackedHere() { v = keep; } } packed{ctx->opt_field_stride, ctx->opt_field_stride};
-  ctx->opt_field_stride = 0;
   const int rc = stage_batch(ctx, "vhp_sweep_batch", src_xy, n_src, dtype == VHP_F64 ? 8 : 4, out_host,
-                             [&](int n) { return vhp_sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out); });
+                             [&](int n) { return sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out, {0, ctx->timing}); });
   return rc == VHP_OK && n_src > 0 ? vhp_sync(ctx) : rc;
 }
 
@@ -872,43 +817,46 @@ static int set_maps_common(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx,
 int vhp_set_maps(vhp_ctx* ctx, const uint8_t* occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, occ, n_maps, nx, ny, false); }
 int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, d_occ, n_maps, nx, ny, true); }
 
-int vhp_sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out) {
+static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out,
+                                   const LaunchOpts& o) {
   if (!ctx || !d_src_xy || !d_map_idx || !d_out || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: bad argument");
-  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch_device: no maps set");
+  if (!ctx->maps.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch_device: no maps set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   if (reinterpret_cast<uintptr_t>(d_out) % (dtype == VHP_F64 ? 8 : 4) != 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: d_out is not aligned to its element type");
-  if (ctx->opt_field_stride > 0 && ctx->opt_field_stride < (long long)ctx->maps_nx * ctx->maps_ny)
+  if (o.field_stride > 0 && o.field_stride < (long long)ctx->maps.nx * ctx->maps.ny)
     return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: field_stride is smaller than a field (nx * ny elements): the fields would overlap");
   if (n_src == 0) return VHP_OK;
   VHP_ON_DEVICE(ctx);
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  const hipError_t e = dtype == VHP_F64 ? launch_maps_sweep<double>(ctx, d_src_xy, d_map_idx, n_src, static_cast<double*>(d_out))
-                                        : launch_maps_sweep<float>(ctx, d_src_xy, d_map_idx, n_src, static_cast<float*>(d_out));
+  const hipError_t e = dtype == VHP_F64 ? launch_maps_sweep<double>(ctx, d_src_xy, d_map_idx, n_src, static_cast<double*>(d_out), o)
+                                        : launch_maps_sweep<float>(ctx, d_src_xy, d_map_idx, n_src, static_cast<float*>(d_out), o);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("maps sweep launch: ") + hipGetErrorString(e));
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
   return VHP_OK;
 }
 
+int vhp_sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out) {
+  return sweep_maps_batch_device(ctx, d_src_xy, d_map_idx, n_src, dtype, d_out, {ctx ? ctx->opt_field_stride : 0, ctx && ctx->timing});
+}
+
 int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host) {
   if (!ctx || !src_xy || !map_idx || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch: bad argument");
-  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch: no maps set");
+  if (!ctx->maps.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch: no maps set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
-  struct PackedHere { long long& v; long long keep; ~PackedHere() { v = keep; } } packed{ctx->opt_field_stride, ctx->opt_field_stride};
-  ctx->opt_field_stride = 0;
-  const size_t field = (size_t)ctx->maps_nx * ctx->maps_ny * (dtype == VHP_F64 ? 8 : 4);
+  const size_t field = (size_t)ctx->maps.nx * ctx->maps.ny * (dtype == VHP_F64 ? 8 : 4);
   int rc = stage_slices(ctx, "vhp_sweep_maps_batch", src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
     const hipError_t e = grow(&ctx->d_map_idx, &ctx->d_map_idx_cap, (size_t)n * sizeof(int32_t), false, ctx->stream);
     if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_sweep_maps_batch: scratch: ") + hipGetErrorString(e));
     VHP_HIP(hipMemcpyAsync(ctx->d_map_idx, map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    return vhp_sweep_maps_batch_device(ctx, ctx->d_src, ctx->d_map_idx, n, dtype, ctx->d_out);
+    return sweep_maps_batch_device(ctx, ctx->d_src, ctx->d_map_idx, n, dtype, ctx->d_out, {0, ctx->timing});
   });
   if (rc != VHP_OK || n_src == 0) return rc;
   rc = vhp_sync(ctx);
   // the sweep leaves a rejected source's field unwritten: zero here, not what the scratch held
   for (int i = 0; i < n_src; ++i) {
     const int x = src_xy[2 * i], y = src_xy[2 * i + 1], k = map_idx[i];
-    if (x < 0 || y < 0 || x >= ctx->maps_nx || y >= ctx->maps_ny || k < 0 || k >= ctx->maps_n)
+    if (x < 0 || y < 0 || x >= ctx->maps.nx || y >= ctx->maps.ny || k < 0 || k >= ctx->maps.n)
       std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
   }
   return rc;
@@ -916,16 +864,16 @@ int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map
 
 int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
   if (!ctx || !out_host) return fail(ctx, VHP_ERR_ARG, "vhp_raycast_all: bad argument");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_raycast_all: no map set");
-  if (src_x < 0 || src_y < 0 || src_x >= ctx->nx || src_y >= ctx->ny) return fail(ctx, VHP_ERR_SOURCE_OOB, "source outside the grid");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_raycast_all: no map set");
+  if (src_x < 0 || src_y < 0 || src_x >= ctx->map.nx || src_y >= ctx->map.ny) return fail(ctx, VHP_ERR_SOURCE_OOB, "source outside the grid");
   VHP_ON_DEVICE(ctx);
-  const size_t cells = (size_t)ctx->nx * ctx->ny;
+  const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
   VHP_HIP(grow(&ctx->d_out, &ctx->d_out_cap, cells * 8, false, ctx->stream));
   double* d = static_cast<double*>(ctx->d_out);
   const unsigned blocks = (unsigned)((cells + 255) / 256);
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   hipLaunchKernelGGL(vhp::vhp_fill_f64, dim3(blocks), dim3(256), 0, ctx->stream, d, 1.0, cells);
-  hipLaunchKernelGGL(vhp::vhp_raycast, dim3(blocks), dim3(256), 0, ctx->stream, ctx->nx, ctx->ny, ctx->d_occ, src_x, src_y, d);
+  hipLaunchKernelGGL(vhp::vhp_raycast, dim3(blocks), dim3(256), 0, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, src_x, src_y, d);
   VHP_HIP(hipGetLastError());
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
@@ -939,8 +887,8 @@ static int union_common(vhp_ctx* ctx, const char* who, const void* d_fields, int
                         void* d_best, int32_t* d_arg) {
   if (!ctx || !d_best || !d_arg || n < 0 || (n > 0 && !d_fields)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad dtype");
-  if (ctx->nx <= 0) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no map set (the grid's size is the map's)");
-  const long long cells = (long long)ctx->nx * ctx->ny;
+  if (ctx->map.nx <= 0) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no map set (the grid's size is the map's)");
+  const long long cells = (long long)ctx->map.nx * ctx->map.ny;
   if (stride == 0) stride = cells;
   if (stride < cells) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": field_stride is smaller than a field");
   const size_t el = dtype == VHP_F64 ? 8 : 4;
@@ -965,30 +913,30 @@ int vhp_union_partials_device(vhp_ctx* ctx, const void* d_bests, const int32_t* 
 
 // ---- MATLAB-flavoured variants (vhp_variant.hip.h) -------------------------------------------------------------------
 static int variant_launch_sweep(vhp_ctx* ctx, const int32_t* d_src, int n_src, double alpha, double fac, double* d_out) {
-  const size_t lds = (size_t)3 * (std::max(ctx->nx, ctx->ny) + 1) * sizeof(double);
+  const size_t lds = (size_t)3 * (std::max(ctx->map.nx, ctx->map.ny) + 1) * sizeof(double);
   auto k = vhp::variant::vhp_variant_sweep;
   hipError_t e = raise_lds_limit(ctx, reinterpret_cast<const void*>(k), lds);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("variant sweep: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(k, dim3((unsigned)(4 * n_src)), dim3(1024), lds, ctx->stream, ctx->nx, ctx->ny, ctx->d_occ, d_src, d_out,
-                     (long long)ctx->nx * ctx->ny, alpha, fac, ctx->d_err);
+  hipLaunchKernelGGL(k, dim3((unsigned)(4 * n_src)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, d_src, d_out,
+                     (long long)ctx->map.nx * ctx->map.ny, alpha, fac, ctx->d_err);
   VHP_HIP(hipGetLastError());
   return VHP_OK;
 }
 
 int vhp_sweep_batch_variant(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double alpha, double fac, double* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(fac > 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_variant: bad argument");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_variant: no map set");
-  if (std::max(ctx->nx, ctx->ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant sweeps: grid side above 4096");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_variant: no map set");
+  if (std::max(ctx->map.nx, ctx->map.ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant sweeps: grid side above 4096");
   return stage_batch(ctx, "vhp_sweep_batch_variant", src_xy, n_src, 8, out_host,
                      [&](int n) { return variant_launch_sweep(ctx, ctx->d_src, n, alpha, fac, static_cast<double*>(ctx->d_out)); });
 }
 
 int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double offset, double* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(offset >= 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_offset: bad argument");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_offset: no map set");
-  if (std::max(ctx->nx, ctx->ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "offset sweeps: grid side above 4096");
-  const size_t cells = (size_t)ctx->nx * ctx->ny;
-  const size_t lds = (size_t)3 * (std::max(ctx->nx, ctx->ny) + 1) * sizeof(double);
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_offset: no map set");
+  if (std::max(ctx->map.nx, ctx->map.ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "offset sweeps: grid side above 4096");
+  const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
+  const size_t lds = (size_t)3 * (std::max(ctx->map.nx, ctx->map.ny) + 1) * sizeof(double);
   auto k = vhp::variant::vhp_offset_sweep;
   bool raised = false;
   return stage_batch(ctx, "vhp_sweep_batch_offset", src_xy, n_src, 8, out_host, [&](int n) -> int {
@@ -998,7 +946,7 @@ int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, doubl
       raised = true;
     }
     VHP_HIP(hipMemsetAsync(ctx->d_out, 0, (size_t)n * cells * 8, ctx->stream));  // a freshly reset() solver
-    hipLaunchKernelGGL(k, dim3((unsigned)(4 * n)), dim3(1024), lds, ctx->stream, ctx->nx, ctx->ny, ctx->d_occ, ctx->d_src,
+    hipLaunchKernelGGL(k, dim3((unsigned)(4 * n)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, ctx->d_src,
                        static_cast<double*>(ctx->d_out), (long long)cells, offset, ctx->d_err);
     VHP_HIP(hipGetLastError());
     return VHP_OK;
@@ -1010,8 +958,8 @@ int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x,
                               uint32_t* n_waypoints) {
   using namespace vhp::variant;
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_variant: no map set");
-  const int nx = ctx->nx, ny = ctx->ny;
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_variant: no map set");
+  const int nx = ctx->map.nx, ny = ctx->map.ny;
   if (std::max(nx, ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant planner: grid side above 4096");
   if ((unsigned)start_x >= (unsigned)nx || (unsigned)start_y >= (unsigned)ny) return fail(ctx, VHP_ERR_START_OOB, "Start point is out of bounds.");
   if ((unsigned)end_x >= (unsigned)nx || (unsigned)end_y >= (unsigned)ny) return fail(ctx, VHP_ERR_END_OOB, "End point is out of bounds.");
@@ -1277,10 +1225,10 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
                       uint64_t max_iter, uint64_t* came_from, double* vis_global, double* vis_local,
                       int32_t* pivots_xy, uint32_t* n_pivots) {
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve: no map set");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve: no map set");
   VHP_ON_DEVICE(ctx);
   std::string msg;
-  vhp::DevMap pm = dev_map(ctx);
+  vhp::DevMap pm = dev_map(ctx->map);
   {
     // one source per sweep: the latency sweep wherever a batch of one would take it (94 against 67 us per sweep at 690^2)
     vhp::SweepPlan plan;
@@ -1289,19 +1237,14 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
     ctx->pl.lat_sweep = nullptr;
     if (plan.kernel == 4)
       ctx->pl.lat_sweep = [ctx](const int32_t* pivots, const int* nb, const int* done, const int* rec, double* out, bool dark_unwritten) {
-        ctx->lat_src_index = nb;
-        ctx->lat_skip = done;
-        ctx->lat_pivot_rec = rec;
-        ctx->lat_dark_unwritten = dark_unwritten;
-        // (no per-launch event pairs inside a planner loop: vhp_timing times sweep launches, and the loop enqueues a batch of
-        // launches past its end that return at once -- they would fill the pool with pairs that time nothing)
-        const bool timing = ctx->timing;
-        ctx->timing = false;
-        const hipError_t e = launch_batch_sweep<double>(ctx, pivots, 1, out, true);
-        ctx->timing = timing;
-        ctx->lat_src_index = ctx->lat_skip = ctx->lat_pivot_rec = nullptr;
-        ctx->lat_dark_unwritten = false;
-        return e;
+        vhp::LatLaunch l;
+        l.src_index = nb;
+        l.skip = done;
+        l.pivot_rec = rec;
+        l.dark_unwritten = dark_unwritten;
+        // (the option's stride, not "packed": one field is written at d_out whatever the stride, but an odd stride takes the sweep's
+        // build for odd pitches -- vhp_lat.hip lat_needs_odd)
+        return launch_batch_sweep<double>(ctx, ctx->map, pivots, 1, out, true, {ctx->opt_field_stride, false}, l);
       };
     // ... or the iteration as ONE launch (vhp_lat.hip vhp_planner_iteration) -- built in round 6, bit-exact, and SLOWER on this part: the
     // epilogue's workgroups sit behind other L2s than the sweep's, so the hand-off inside a launch costs an L2 write-back and an
@@ -1311,17 +1254,11 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
     static const bool one_kernel = std::getenv("VHP_PLANNER_ONE_KERNEL") != nullptr;
     if (ctx->pl.lat_sweep && one_kernel)
       ctx->pl.lat_iteration = [ctx](const vhp::PlannerDev& d) {
-        ctx->lat_pivot_rec = d.rec;
-        ctx->lat_dark_unwritten = true;
-        ctx->planner_dev = &d;
-        const bool timing = ctx->timing;
-        ctx->timing = false;
-        const hipError_t e = launch_batch_sweep<double>(ctx, d.pivots, 1, d.vis_local, true);
-        ctx->timing = timing;
-        ctx->planner_dev = nullptr;
-        ctx->lat_pivot_rec = nullptr;
-        ctx->lat_dark_unwritten = false;
-        return e;
+        vhp::LatLaunch l;
+        l.pivot_rec = d.rec;
+        l.dark_unwritten = true;
+        l.planner_dev = &d;
+        return launch_batch_sweep<double>(ctx, ctx->map, d.pivots, 1, d.vis_local, true, {ctx->opt_field_stride, false}, l);
       };
   }
   ctx->pl.path_state = 0;
@@ -1337,10 +1274,10 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
                                   int mode, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy,
                                   uint32_t* n_pivots, int32_t* stats) {
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_speculative: no map set");
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_speculative: no map set");
   VHP_ON_DEVICE(ctx);
   std::string msg;
-  vhp::DevMap pm = dev_map(ctx);
+  vhp::DevMap pm = dev_map(ctx->map);
   {
     // k sources per launch: the latency sweep (8 k workgroups) wherever a batch of k would take it
     vhp::SweepPlan plan;
@@ -1349,20 +1286,12 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
     ctx->pl.lat_sweep_k = nullptr;
     if (plan.kernel == 4)
       ctx->pl.lat_sweep_k = [ctx](const int32_t* cand, int n, const int* slot_base, const int* run_if, const int* done, double* cache, bool dark_unwritten) {
-        ctx->lat_skip = done;
-        ctx->lat_slot_base = slot_base;
-        ctx->lat_run_if = run_if;
-        ctx->lat_dark_unwritten = dark_unwritten;
-        const long long stride = ctx->opt_field_stride;
-        ctx->opt_field_stride = 0;  // (the cache holds packed fields)
-        const bool timing = ctx->timing;
-        ctx->timing = false;  // (as in vhp_planner_solve's loop)
-        const hipError_t e = launch_batch_sweep<double>(ctx, cand, n, cache, true);
-        ctx->timing = timing;
-        ctx->opt_field_stride = stride;
-        ctx->lat_skip = ctx->lat_slot_base = ctx->lat_run_if = nullptr;
-        ctx->lat_dark_unwritten = false;
-        return e;
+        vhp::LatLaunch l;
+        l.skip = done;
+        l.slot_base = slot_base;
+        l.run_if = run_if;
+        l.dark_unwritten = dark_unwritten;
+        return launch_batch_sweep<double>(ctx, ctx->map, cand, n, cache, true, {}, l);  // (the cache holds packed fields)
       };
   }
   int st[3] = {0, 0, 0};
@@ -1392,165 +1321,111 @@ int vhp_planner_results_device(vhp_ctx* ctx, const uint32_t** labels, const doub
   return VHP_OK;
 }
 
-int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* thresholds, int n_queries, uint64_t max_iter,
-                            int32_t* status, uint32_t* n_pivots) {
+// vhp_planner_solve_batch on the single map and, with `maps`, vhp_planner_solve_maps_batch on the stack (query q on map map_idx[q]).
+static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const int32_t* map_idx, const double* thresholds, int n_queries,
+                       uint64_t max_iter, int32_t* status, uint32_t* n_pivots) {
   if (!ctx) return VHP_ERR_ARG;
-  if (n_queries < 1 || n_queries > vhp::kBatchMaxQueries) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_batch: n_queries outside 1..64");
-  if (!queries || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_batch: null array");
+  const std::string who = maps ? "vhp_planner_solve_maps_batch" : "vhp_planner_solve_batch";
+  if (n_queries < 1 || n_queries > vhp::kBatchMaxQueries) return fail(ctx, VHP_ERR_ARG, who + ": n_queries outside 1..64");
+  if (!queries || (maps && !map_idx) || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, who + ": null array");
   if (max_iter > (1u << 24)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
-  if (!ctx->d_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_batch: no map set");
+  const auto [b, m, none_solved] = batch_on(ctx, maps);
+  if (!m.rows) return fail(ctx, VHP_ERR_NO_MAP, who + (maps ? ": no maps set" : ": no map set"));
+  for (int q = 0; maps && q < n_queries; ++q)
+    if (map_idx[q] < 0 || map_idx[q] >= m.n) return fail(ctx, VHP_ERR_ARG, who + ": query " + std::to_string(q) + ": map index outside the stack");
   VHP_ON_DEVICE(ctx);
-  vhp::DevMap pm = dev_map(ctx);
-  vhp::BatchState& b = ctx->batch;
-  const int G = planner_batch_group_size(ctx, ctx->nx, ctx->ny, max_iter);
+  vhp::DevMap pm = dev_map(m);
+  const int G = planner_batch_group_size(ctx, m, max_iter);
   b.lat_sweep = nullptr;
   b.front_sweep = nullptr;
   if (G > 0) {
-    b.lat_sweep = [ctx](const int32_t* cand, const int32_t*, int n, double* out) {
-      ctx->lat_slot_base = reinterpret_cast<const int*>(ctx->batch.n_done + 1);   // (a zero: field g of the launch is query g's)
-      ctx->lat_dark_unwritten = true;
-      const long long stride = ctx->opt_field_stride;
-      ctx->opt_field_stride = 0;  // (the queries' local fields are packed)
-      const bool timing = ctx->timing;
-      ctx->timing = false;  // (as in vhp_planner_solve's loop)
-      const hipError_t e = launch_batch_sweep<double>(ctx, cand, n, out, true);
-      ctx->timing = timing;
-      ctx->opt_field_stride = stride;
-      ctx->lat_slot_base = nullptr;
-      ctx->lat_dark_unwritten = false;
-      return e;
-    };
-    ctx->last_kernel = 4;
-  } else {
-    const vhp::SweepPlan plan = plan_for(ctx, 1, true);
-    hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
-    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
-    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int) {
-      switch (plan.R) {
-        case 1: return plan.multi ? launch_batch_fronts<1, true>(ctx, pm, d, plan.W) : launch_batch_fronts<1, false>(ctx, pm, d, plan.W);
-        case 2: return plan.multi ? launch_batch_fronts<2, true>(ctx, pm, d, plan.W) : launch_batch_fronts<2, false>(ctx, pm, d, plan.W);
-        default: return plan.multi ? launch_batch_fronts<4, true>(ctx, pm, d, plan.W) : launch_batch_fronts<4, false>(ctx, pm, d, plan.W);
-      }
-    };
-    ctx->last_kernel = 1;
-  }
-  std::string msg;
-  const int rc = vhp::planner_solve_batch(b, pm, ctx->d_occ, ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream, ctx->ev0,
-                                          ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg);
-  ctx->timed = true;
-  if (!msg.empty()) ctx->err = msg;
-  return rc;
-}
-
-int vhp_planner_batch_group(const vhp_ctx* ctx) { return ctx && ctx->batch.solved ? ctx->batch.group : 0; }
-
-int vhp_planner_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
-                                     const int32_t** pivots_xy) {
-  if (!ctx) return VHP_ERR_ARG;
-  int k = 0;
-  if (int rc = batch_slot(ctx, "vhp_planner_batch_results_device", q, &k); rc != VHP_OK) return rc;
-  vhp::batch_results_device(ctx->batch, k, labels, vis_global, vis_local, pivots_xy);
-  return VHP_OK;
-}
-
-int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
-  if (!ctx) return VHP_ERR_ARG;
-  int k = 0;
-  if (int rc = batch_slot(ctx, "vhp_planner_batch_results", q, &k); rc != VHP_OK) return rc;
-  VHP_ON_DEVICE(ctx);
-  std::string msg;
-  const int rc = vhp::batch_results_host(ctx->batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
-  if (rc != VHP_OK) ctx->err = msg;
-  return rc;
-}
-
-int vhp_planner_solve_maps_batch(vhp_ctx* ctx, const int32_t* queries, const int32_t* map_idx, const double* thresholds, int n_queries,
-                                 uint64_t max_iter, int32_t* status, uint32_t* n_pivots) {
-  if (!ctx) return VHP_ERR_ARG;
-  if (n_queries < 1 || n_queries > vhp::kBatchMaxQueries) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: n_queries outside 1..64");
-  if (!queries || !map_idx || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: null array");
-  if (max_iter > (1u << 24)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
-  if (!ctx->d_maps_rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_maps_batch: no maps set");
-  for (int q = 0; q < n_queries; ++q)
-    if (map_idx[q] < 0 || map_idx[q] >= ctx->maps_n)
-      return fail(ctx, VHP_ERR_ARG, "vhp_planner_solve_maps_batch: query " + std::to_string(q) + ": map index outside the stack");
-  VHP_ON_DEVICE(ctx);
-  const int nx = ctx->maps_nx, ny = ctx->maps_ny;
-  vhp::DevMap pm = stack_dev_map(ctx);
-  vhp::BatchState& b = ctx->maps_batch;
-  const int G = planner_batch_group_size(ctx, nx, ny, max_iter);
-  b.lat_sweep = nullptr;
-  b.front_sweep = nullptr;
-  if (G > 0) {
-    if (!ctx->d_maps_dmap) {  // (the stack's diagonal maps: built once, by the first batch that sweeps them)
-      VHP_HIP(hipMalloc(&ctx->d_maps_dmap, vhp::lat_diag_map_bytes(nx, ny) * ctx->maps_n));
-      const hipError_t e = vhp::lat_pack_diag_stack(ctx->d_maps_rows, ctx->maps_n, nx, ny, ctx->maps_wpr, ctx->d_maps_dmap, ctx->stream);
+    if (maps && !m.dmap) {  // (the stack's diagonal maps: built once, by the first batch that sweeps them)
+      VHP_HIP(hipMalloc(&m.dmap, vhp::lat_diag_map_bytes(m.nx, m.ny) * m.n));
+      const hipError_t e = vhp::lat_pack_diag_stack(m.rows, m.n, m.nx, m.ny, m.wpr, m.dmap, ctx->stream);
       if (e != hipSuccess) {
-        (void)hipFree(ctx->d_maps_dmap);
-        ctx->d_maps_dmap = nullptr;
-        return fail(ctx, VHP_ERR_HIP, std::string("vhp_planner_solve_maps_batch: diagonal maps: ") + hipGetErrorString(e));
+        (void)hipFree(m.dmap);
+        m.dmap = nullptr;
+        return fail(ctx, VHP_ERR_HIP, who + ": diagonal maps: " + hipGetErrorString(e));
       }
     }
-    b.lat_sweep = [ctx](const int32_t* cand, const int32_t* d_map_idx, int n, double* out) {
-      ctx->lat_slot_base = reinterpret_cast<const int*>(ctx->maps_batch.n_done + 1);   // (a zero: field g of the launch is query g's)
-      ctx->lat_dark_unwritten = true;
-      const long long stride = ctx->opt_field_stride;
-      ctx->opt_field_stride = 0;  // (the queries' local fields are packed)
-      const bool timing = ctx->timing;
-      ctx->timing = false;  // (as in vhp_planner_solve's loop)
-      const hipError_t e = launch_batch_sweep<double>(ctx, cand, n, out, true, d_map_idx);
-      ctx->timing = timing;
-      ctx->opt_field_stride = stride;
-      ctx->lat_slot_base = nullptr;
-      ctx->lat_dark_unwritten = false;
-      return e;
+    vhp::BatchState* bs = &b;
+    vhp::PackedMaps* pk = &m;
+    b.lat_sweep = [ctx, bs, pk](const int32_t* cand, const int32_t* d_map_idx, int n, double* out) {
+      vhp::LatLaunch l;
+      l.slot_base = reinterpret_cast<const int*>(bs->n_done + 1);  // (a zero: field g of the launch is query g's)
+      l.dark_unwritten = true;
+      l.map_idx = d_map_idx;  // (null on the single map)
+      return launch_batch_sweep<double>(ctx, *pk, cand, n, out, true, {}, l);  // (the queries' local fields are packed)
     };
     ctx->last_kernel = 4;
   } else {
-    const vhp::SweepPlan plan = plan_for_grid(ctx, nx, ny, 1, true);
+    const vhp::SweepPlan plan = plan_for_grid(ctx, m, 1, true);
     hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
     if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
     b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int k) {
-      vhp::DevMap mk = pm;  // (map k of the stack: map 0's packed copies moved by k strides)
+      vhp::DevMap mk = pm;  // (map k of the stack: map 0's packed copies moved by k strides; k is 0 on the single map)
       mk.rows += (size_t)k * mk.ny * mk.wpr;
       mk.cols += (size_t)k * mk.nx * mk.wpc;
-      switch (plan.R) {
-        case 1: return plan.multi ? launch_batch_fronts<1, true>(ctx, mk, d, plan.W) : launch_batch_fronts<1, false>(ctx, mk, d, plan.W);
-        case 2: return plan.multi ? launch_batch_fronts<2, true>(ctx, mk, d, plan.W) : launch_batch_fronts<2, false>(ctx, mk, d, plan.W);
-        default: return plan.multi ? launch_batch_fronts<4, true>(ctx, mk, d, plan.W) : launch_batch_fronts<4, false>(ctx, mk, d, plan.W);
-      }
+      return vhp::with_sweep_shape(plan.R, plan.multi, [&](auto r, auto mr) { return launch_batch_fronts<r(), mr()>(ctx, mk, d, plan.W); });
     };
     ctx->last_kernel = 1;
   }
-  const vhp::BatchStack st{map_idx, ctx->d_maps_rows, (long long)ny * ctx->maps_wpr, ctx->maps_wpr};
+  const vhp::BatchStack st{map_idx, m.rows, (long long)m.ny * m.wpr, m.wpr};
   std::string msg;
-  const int rc = vhp::planner_solve_batch(b, pm, nullptr, nullptr, ctx->stream, ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter,
-                                          G > 0 ? G : 1, status, n_pivots, &msg, &st);
+  const int rc = vhp::planner_solve_batch(b, pm, maps ? nullptr : ctx->d_occ, maps || ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream,
+                                          ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg,
+                                          maps ? &st : nullptr);
   ctx->timed = true;
   if (!msg.empty()) ctx->err = msg;
   return rc;
 }
 
-int vhp_planner_maps_batch_group(const vhp_ctx* ctx) { return ctx && ctx->maps_batch.solved ? ctx->maps_batch.group : 0; }
-
-int vhp_planner_maps_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
-                                          const int32_t** pivots_xy) {
+static int batch_results_device(vhp_ctx* ctx, const char* who, bool maps, int q, const uint32_t** labels, const double** vis_global,
+                                const double** vis_local, const int32_t** pivots_xy) {
   if (!ctx) return VHP_ERR_ARG;
   int k = 0;
-  if (int rc = batch_slot(ctx, "vhp_planner_maps_batch_results_device", q, &k, true); rc != VHP_OK) return rc;
-  vhp::batch_results_device(ctx->maps_batch, k, labels, vis_global, vis_local, pivots_xy);
+  if (int rc = batch_slot(ctx, who, maps, q, &k); rc != VHP_OK) return rc;
+  vhp::batch_results_device(batch_on(ctx, maps).b, k, labels, vis_global, vis_local, pivots_xy);
   return VHP_OK;
 }
 
-int vhp_planner_maps_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
+static int batch_results(vhp_ctx* ctx, const char* who, bool maps, int q, uint64_t* came_from, double* vis_global, double* vis_local,
+                         int32_t* pivots_xy) {
   if (!ctx) return VHP_ERR_ARG;
   int k = 0;
-  if (int rc = batch_slot(ctx, "vhp_planner_maps_batch_results", q, &k, true); rc != VHP_OK) return rc;
+  if (int rc = batch_slot(ctx, who, maps, q, &k); rc != VHP_OK) return rc;
   VHP_ON_DEVICE(ctx);
   std::string msg;
-  const int rc = vhp::batch_results_host(ctx->maps_batch, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
+  const int rc = vhp::batch_results_host(batch_on(ctx, maps).b, k, ctx->stream, came_from, vis_global, vis_local, pivots_xy, &msg);
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
+}
+
+static int batch_group(const vhp::BatchState& b) { return b.solved ? b.group : 0; }
+
+int vhp_planner_solve_batch(vhp_ctx* ctx, const int32_t* queries, const double* thresholds, int n_queries, uint64_t max_iter,
+                            int32_t* status, uint32_t* n_pivots) {
+  return solve_batch(ctx, false, queries, nullptr, thresholds, n_queries, max_iter, status, n_pivots);
+}
+int vhp_planner_solve_maps_batch(vhp_ctx* ctx, const int32_t* queries, const int32_t* map_idx, const double* thresholds, int n_queries,
+                                 uint64_t max_iter, int32_t* status, uint32_t* n_pivots) {
+  return solve_batch(ctx, true, queries, map_idx, thresholds, n_queries, max_iter, status, n_pivots);
+}
+int vhp_planner_batch_group(const vhp_ctx* ctx) { return ctx ? batch_group(ctx->batch) : 0; }
+int vhp_planner_maps_batch_group(const vhp_ctx* ctx) { return ctx ? batch_group(ctx->maps_batch) : 0; }
+int vhp_planner_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
+                                     const int32_t** pivots_xy) {
+  return batch_results_device(ctx, "vhp_planner_batch_results_device", false, q, labels, vis_global, vis_local, pivots_xy);
+}
+int vhp_planner_maps_batch_results_device(vhp_ctx* ctx, int q, const uint32_t** labels, const double** vis_global, const double** vis_local,
+                                          const int32_t** pivots_xy) {
+  return batch_results_device(ctx, "vhp_planner_maps_batch_results_device", true, q, labels, vis_global, vis_local, pivots_xy);
+}
+int vhp_planner_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
+  return batch_results(ctx, "vhp_planner_batch_results", false, q, came_from, vis_global, vis_local, pivots_xy);
+}
+int vhp_planner_maps_batch_results(vhp_ctx* ctx, int q, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy) {
+  return batch_results(ctx, "vhp_planner_maps_batch_results", true, q, came_from, vis_global, vis_local, pivots_xy);
 }
 
 int vhp_planner_batch_paths(vhp_ctx* ctx, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* path_status) {

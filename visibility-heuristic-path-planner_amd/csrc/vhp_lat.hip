@@ -228,14 +228,14 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   auto k = halves > 1 ? (odd ? vhp_lat_sweep<OutT, true, true> : vhp_lat_sweep<OutT, false, true>)
                       : (odd ? vhp_lat_sweep<OutT, true, false> : vhp_lat_sweep<OutT, false, false>);
 #endif
-  // a stack of maps (a.d_map_idx): the fp64 build of the kernel that reads a map per source
+  // a stack of maps (a.lat.map_idx): the fp64 build of the kernel that reads a map per source
   auto ks = halves > 1 ? (odd ? vhp_lat_maps_sweep<true, true> : vhp_lat_maps_sweep<false, true>)
                        : (odd ? vhp_lat_maps_sweep<true, false> : vhp_lat_maps_sweep<false, false>);
-  if (a.d_map_idx && (sizeof(OutT) != 8 || pd)) return hipErrorInvalidValue;
+  if (a.lat.map_idx && (sizeof(OutT) != 8 || pd)) return hipErrorInvalidValue;
   const size_t lds = lat_lds_bytes(a.nx, a.ny);
   if (lds > kLdsLimit || a.pool_epoch == 0) return hipErrorInvalidValue;
   if (a.raise_lds) {
-    hipError_t e = a.raise_lds(a.d_map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), lds);
+    hipError_t e = a.raise_lds(a.lat.map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return e;
   }
 #ifdef VHP_EXP_ONE_KERNEL
@@ -256,12 +256,12 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   g.lines = reinterpret_cast<vhp::lanes::Tagged*>(a.d_queue);
   g.unit_blocks = lat_unit_blocks(a.nx, a.ny);
   g.epoch = a.pool_epoch;
-  g.src_index = a.d_src_index;
-  g.skip = a.d_skip;
-  g.pivot_rec = a.d_pivot_rec;
-  g.slot_base = a.d_slot_base;
-  g.run_if = a.d_run_if;
-  g.dead_cells_are_zero = a.lat_dead_cells_are_zero;
+  g.src_index = a.lat.src_index;
+  g.skip = a.lat.skip;
+  g.pivot_rec = a.lat.pivot_rec;
+  g.slot_base = a.lat.slot_base;
+  g.run_if = a.lat.run_if;
+  g.dead_cells_are_zero = a.lat.dark_unwritten;
   g.strip_times = nullptr;
   g.dmap = a.dmap;
   if (!g.dmap) return hipErrorInvalidValue;
@@ -289,15 +289,15 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
     }
   }
 #endif
-  if (g.halves == 1 && a.n_src * kUnits > (a.n_cus > 0 ? a.n_cus : 256) && a.n_src * kUnits <= 1024 * pool::kLatOrderPerThread && a.d_lat_order && !a.d_pivot_rec && !a.d_src_index && !a.d_slot_base) {
+  if (g.halves == 1 && a.n_src * kUnits > (a.n_cus > 0 ? a.n_cus : 256) && a.n_src * kUnits <= 1024 * pool::kLatOrderPerThread && a.d_lat_order && !a.lat.pivot_rec && !a.lat.src_index && !a.lat.slot_base) {
     // more workgroups than the chip holds at once: the long units first
     // (a list of its own, not a corner of the scratch: nothing but tagged entries may ever be written where a later launch looks for tags)
     hipLaunchKernelGGL(pool::vhp_lat_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, a.d_lat_order);
     g.order = a.d_lat_order;
   }
-  if (a.d_map_idx) {
+  if (a.lat.map_idx) {
     if constexpr (sizeof(OutT) == 8) {
-      const LatMapStack st{a.d_map_idx, a.n_maps, (long long)a.ny * a.wpr, (long long)a.nx * a.wpc, (long long)DiagMaps::words(a.nx, a.ny)};
+      const LatMapStack st{a.lat.map_idx, a.n_maps, (long long)a.ny * a.wpr, (long long)a.nx * a.wpc, (long long)DiagMaps::words(a.nx, a.ny)};
       hipLaunchKernelGGL(ks, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g, st);
     }
   } else {
@@ -346,12 +346,11 @@ extern "C" int vhp_debug_read_lat_strip_times(unsigned long long* dst, int n_wor
 
 hipError_t launch_lat(const BatchArgs& a) {
   if (!lat_supported(a.nx, a.ny)) return hipErrorInvalidValue;
+  if (a.lat.planner_dev) {
+    if (a.dtype != VHP_F64 || a.n_src != 1 || !a.lat.pivot_rec) return hipErrorInvalidValue;
+    return launch_lat_t<double>(a, a.lat.planner_dev);
+  }
   return a.dtype == VHP_F64 ? launch_lat_t<double>(a) : launch_lat_t<float>(a);
-}
-
-hipError_t launch_lat_planner(const BatchArgs& a, const PlannerDev& d) {
-  if (!lat_supported(a.nx, a.ny) || a.dtype != VHP_F64 || a.n_src != 1 || !a.d_pivot_rec) return hipErrorInvalidValue;
-  return launch_lat_t<double>(a, &d);
 }
 
 }  // namespace vhp

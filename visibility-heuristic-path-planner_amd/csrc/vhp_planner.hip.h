@@ -298,9 +298,7 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
           continue;
         }
         hipError_t e = s.lat_sweep ? s.lat_sweep(d.pivots, &s.ctl->nb, &s.ctl->done, d.rec, d.vis_local, true)
-                     : R == 1 ? (multi ? launch_planner_fronts<1, true>(s, m, d, W, stream) : launch_planner_fronts<1, false>(s, m, d, W, stream))
-                     : R == 2 ? (multi ? launch_planner_fronts<2, true>(s, m, d, W, stream) : launch_planner_fronts<2, false>(s, m, d, W, stream))
-                              : (multi ? launch_planner_fronts<4, true>(s, m, d, W, stream) : launch_planner_fronts<4, false>(s, m, d, W, stream));
+                                   : with_sweep_shape(R, multi, [&](auto r, auto mr) { return launch_planner_fronts<r(), mr()>(s, m, d, W, stream); });
         if (e != hipSuccess) { *msg = std::string("planner launch: ") + hipGetErrorString(e); return VHP_ERR_HIP; }
         hipLaunchKernelGGL(vhp_planner_epilogue, dim3(kEpilogueBlocks), dim3(kEpilogueThreads), 0, stream, m, d);
         VHP_PL_HIP(hipGetLastError());
@@ -850,9 +848,7 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
     const int rc = planner_poll(s, stream, [&]() -> int {
       for (int b = 0; b < batch; ++b) {
         hipError_t e = s.lat_sweep_k ? s.lat_sweep_k(ss.sc->cand, K, &ss.sc->cur_slot, &ss.sc->sweep, &s.ctl->done, ss.cache, mode == 1)
-                     : R == 1 ? (multi ? launch_spec_fronts<1, true>(s, m, d, sp, W, stream) : launch_spec_fronts<1, false>(s, m, d, sp, W, stream))
-                     : R == 2 ? (multi ? launch_spec_fronts<2, true>(s, m, d, sp, W, stream) : launch_spec_fronts<2, false>(s, m, d, sp, W, stream))
-                              : (multi ? launch_spec_fronts<4, true>(s, m, d, sp, W, stream) : launch_spec_fronts<4, false>(s, m, d, sp, W, stream));
+                                     : with_sweep_shape(R, multi, [&](auto r, auto mr) { return launch_spec_fronts<r(), mr()>(s, m, d, sp, W, stream); });
         if (e != hipSuccess) { *msg = std::string("speculative planner launch: ") + hipGetErrorString(e); return VHP_ERR_HIP; }
         auto epi = mode == 0 ? vhp_spec_epilogue<1, false> : K == 1 ? vhp_spec_epilogue<1, true> : K == 2 ? vhp_spec_epilogue<2, true>
                            : K == 4 ? vhp_spec_epilogue<4, true> : vhp_spec_epilogue<8, true>;

@@ -1015,6 +1015,17 @@ inline size_t sweep_lds_bytes(int R, int W, bool multi = false, bool pack = fals
   return d * sizeof(double);
 }
 
+// A plan's front-sweep shape (R: 1, 2, else 4; multi) as template arguments: f(std::integral_constant<int, R>, std::bool_constant<MULTI>).
+template <typename F>
+inline hipError_t with_sweep_shape(int R, bool multi, F f) {
+  using std::integral_constant;
+  switch (R) {
+    case 1: return multi ? f(integral_constant<int, 1>{}, std::true_type{}) : f(integral_constant<int, 1>{}, std::false_type{});
+    case 2: return multi ? f(integral_constant<int, 2>{}, std::true_type{}) : f(integral_constant<int, 2>{}, std::false_type{});
+    default: return multi ? f(integral_constant<int, 4>{}, std::true_type{}) : f(integral_constant<int, 4>{}, std::false_type{});
+  }
+}
+
 // One quadrant of one source: called by all 2*W wavefronts of a workgroup.
 // Q1 (+,+) Q2 (-,+) Q3 (-,-) Q4 (+,-), reference solver.cpp:575-695.
 template <int R, int DX, int DY, typename Emit>
