@@ -329,14 +329,17 @@ int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, doubl
 /* Elapsed milliseconds between the first and last kernel of the most recent
  * vhp_sweep_batch_device / planner call, from hipEvents recorded on the context
  * stream.  Blocks until that work has finished.  vhp_probe_stores and vhp_alloc_output time their probes with the same pair of
- * events: after either of them there is nothing to report (VHP_ERR_ARG, "nothing timed yet") until the next sweep or solve. */
+ * events: after either of them there is nothing to report (VHP_ERR_ARG, "nothing timed yet") until the next sweep or solve.
+ * The events carry no system-scope fence (hipEventDisableSystemFence): the call reports a time and is no point behind which the
+ * host may read what the work wrote -- that is vhp_sync, hipStreamSynchronize or a copy on the stream. */
 int vhp_last_elapsed_ms(vhp_ctx* ctx, float* ms);
 
 /* Per-launch kernel timing for benchmarks.  vhp_timing(ctx, 1) makes every following
  * vhp_sweep_batch_device call bracket what it launches -- the unit-ordering pre-kernel and the
  * sweep kernel -- with a pair of hipEvents on the context stream; vhp_timing_collect waits for them,
  * writes up to `cap` durations in milliseconds (oldest first), returns their count in *n and
- * clears the list.  vhp_timing(ctx, 0) switches it off. */
+ * clears the list.  vhp_timing(ctx, 0) switches it off.  These events carry no system-scope fence (hipEventDisableSystemFence:
+ * recording one costs the launches around it no cache write-back) and are for timing only: waiting for them orders no memory. */
 int vhp_timing(vhp_ctx* ctx, int enable);  /* enable > 1: also pre-creates that many event pairs */
 int vhp_timing_collect(vhp_ctx* ctx, float* ms_out, int cap, int* n);
 

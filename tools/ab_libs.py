@@ -2,8 +2,15 @@
 side, alternates blocks of launches between them and prints the median kernel time per build.  Diagnostic only.
 usage: ab_libs.py <side> <n sources> <lib>[@key=value,...] ...      ("-" = the in-tree build; the keys are vhp_set_option
 keys, e.g. -@kernel=1 exp/libvhp_NOSTORE.so@kernel=2, or the launch shapes: -@rows_per_lane=1,strips=8).
-Set AB_DTYPE=f32 in the environment for fp32 fields."""
-import os, sys
+Set AB_DTYPE=f32 in the environment for fp32 fields.
+With --wall in front of <side>: wall clock instead -- per alternation 200 launches (AB_STEPS) back to back with vhp_timing on, as
+bench.py's timed region runs them, between two synchronizes; six alternations count (AB_REPS, the first one more is dropped).  Prints
+per build the median and the range of the wall time per launch, of the event-pair time and of their difference, and whether every
+run of each later build beat every run of the first one."""
+import os, sys, time
+WALL = len(sys.argv) > 1 and sys.argv[1] == "--wall"
+if WALL:
+    del sys.argv[1]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -36,6 +43,42 @@ for lib in libs:
     for k, v in shapes[lib]:
         c.set_option(k, int(v))
     ctxs.append(c)
+def wall_ab():
+    steps, reps = int(os.environ.get("AB_STEPS", "200")), int(os.environ.get("AB_REPS", "6"))
+    dt = mod.F32 if F32 else mod.F64
+    wall, kern = {l: [] for l in libs}, {l: [] for l in libs}
+    for rep in range(reps + 1):
+        for lib, ctx in zip(libs, ctxs):
+            for _ in range(5):
+                ctx.sweep_batch_device(d_src.data_ptr(), n, out.data_ptr(), dtype=dt)
+            torch.cuda.synchronize()
+            ctx.timing(True, prealloc=steps + 2)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ctx.sweep_batch_device(d_src.data_ptr(), n, out.data_ptr(), dtype=dt)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            k = ctx.timing_collect(steps)
+            ctx.timing(False)
+            if rep:
+                wall[lib].append(el / steps * 1e6)
+                kern[lib].append(float(k.sum()) / steps * 1e3)
+    fmt = lambda v: "median %.1f (%.1f .. %.1f)" % (np.median(v), min(v), max(v))
+    for lib in libs:
+        gap = [w - k for w, k in zip(wall[lib], kern[lib])]
+        print("side %d n %d lib [%s], us per launch over %d x %d launches: wall %s; event pairs %s; wall - pairs %s" % (
+            side, n, lib, len(wall[lib]), steps, fmt(wall[lib]), fmt(kern[lib]), fmt(gap)))
+        print("    wall by alternation: %s" % " ".join("%.1f" % x for x in wall[lib]))
+    for lib in libs[1:]:
+        print("[%s] against [%s]: %s; medians %.1f against %.1f us (%+.2f %%)" % (
+            lib, libs[0], "every run faster than every run of the first" if max(wall[lib]) < min(wall[libs[0]]) else
+            "every run slower than every run of the first" if min(wall[lib]) > max(wall[libs[0]]) else "the ranges overlap",
+            np.median(wall[lib]), np.median(wall[libs[0]]), 100.0 * (np.median(wall[lib]) / np.median(wall[libs[0]]) - 1.0)))
+
+
+if WALL:
+    wall_ab()
+    sys.exit(0)
 res = {l: [] for l in libs}
 for rep in range(6):
     for lib, ctx in zip(libs, ctxs):

@@ -221,14 +221,26 @@ struct LaunchOpts {
   bool timed = false;
 };
 
+// The library's timing events -- the context's ev0 / ev1 and vhp_timing's pairs -- carry no system-scope fence.  A plain hipEvent
+// releases to the system when it is recorded: a cache write-back and invalidate between one launch's sweep and the next launch's
+// order kernel, twice per pair.  Nothing needs it here: every wait on one of these events (vhp_timing_collect, vhp_last_elapsed_ms,
+// vhp_probe_stores) is followed by hipEventElapsedTime and by no read of memory; what the host or another stream reads, it reads
+// behind hipStreamSynchronize, a copy or a kernel boundary, which order memory by themselves.  The events something is read on the
+// strength of (the planners' poll events, the multi-device `done` events) are created elsewhere and keep their fence.
+// (VHP_TIMING_EVENT_FLAGS: hipEventReleaseToDevice or 0 for an A/B build, tools/ab_libs.py)
+#ifndef VHP_TIMING_EVENT_FLAGS
+#define VHP_TIMING_EVENT_FLAGS hipEventDisableSystemFence
+#endif
+hipError_t create_timing_event(hipEvent_t* e) { return hipEventCreateWithFlags(e, VHP_TIMING_EVENT_FLAGS); }
+
 // A timed launch's events (else none): a recycled pair, or a new one.
 using EventPair = std::pair<hipEvent_t, hipEvent_t>;
 hipError_t acquire_events(vhp_ctx* c, bool timed, EventPair* ev) {
   *ev = {nullptr, nullptr};
   if (!timed) return hipSuccess;
   if (!c->event_pool.empty()) { *ev = c->event_pool.back(); c->event_pool.pop_back(); return hipSuccess; }
-  if (hipEventCreate(&ev->first) != hipSuccess) return hipErrorOutOfMemory;
-  if (hipEventCreate(&ev->second) == hipSuccess) return hipSuccess;
+  if (create_timing_event(&ev->first) != hipSuccess) return hipErrorOutOfMemory;
+  if (create_timing_event(&ev->second) == hipSuccess) return hipSuccess;
   (void)hipEventDestroy(ev->first);
   return hipErrorOutOfMemory;
 }
@@ -677,7 +689,7 @@ int vhp_create(int device_ordinal, vhp_ctx** out) {
   ctx->device = device_ordinal;
   DeviceGuard guard(device_ordinal);
   if (!guard.ok || hipStreamCreate(&ctx->own_stream) != hipSuccess ||
-      hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
+      create_timing_event(&ctx->ev0) != hipSuccess || create_timing_event(&ctx->ev1) != hipSuccess ||
       hipMalloc(&ctx->d_err, sizeof(int)) != hipSuccess || hipMemset(ctx->d_err, 0, sizeof(int)) != hipSuccess) {
     delete ctx;
     return VHP_ERR_HIP;
@@ -1032,8 +1044,11 @@ int vhp_timing(vhp_ctx* ctx, int enable) {
     VHP_ON_DEVICE(ctx);
     while ((int)ctx->event_pool.size() < enable) {
       hipEvent_t a = nullptr, b = nullptr;
-      VHP_HIP(hipEventCreate(&a));
-      VHP_HIP(hipEventCreate(&b));
+      VHP_HIP(create_timing_event(&a));
+      if (const hipError_t eb = create_timing_event(&b); eb != hipSuccess) {
+        (void)hipEventDestroy(a);
+        VHP_HIP(eb);
+      }
       ctx->event_pool.push_back({a, b});
     }
   }

@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, i
 // are rejected when they are installed).  If the lines do not fit `capacity_blocks` (the launcher sizes the scratch by an upper
 // bound, so they do) nothing is swept and the error flag says so.
 constexpr int kBuckets = 1024;
-constexpr int kOrderLdsUnits = 8192;  // batches of up to 1024 sources keep the per-unit scratch of the ordering in LDS
+constexpr int kOrderLdsUnits = 8192;  // batches of up to 1024 sources are ordered in LDS alone (order_units_lds)
 
 // exclusive prefix sums over arr[0..n), in place, by the 1024 threads of the workgroup (a contiguous chunk each); returns the total
 template <typename Arr>
@@ -69,7 +69,7 @@ __device__ __forceinline__ int block_exclusive_scan_1024(Arr arr, int n, int* wa
   return all;
 }
 
-// (PerUnit: int* in LDS, or line_base itself in global memory for batches whose units do not fit there)
+// (batches of more than kOrderLdsUnits units; PerUnit: line_base itself, in global memory)
 template <typename PerUnit>
 __device__ __forceinline__ void order_units(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order,
                                             int* __restrict__ line_base, int* __restrict__ recs, long long capacity_blocks,
@@ -127,15 +127,94 @@ __device__ __forceinline__ void order_units(const int32_t* __restrict__ src_xy, 
   }
 }
 
+// The same ordering for batches of up to kOrderLdsUnits units (1024 sources), without a round trip through global memory: every thread
+// owns a contiguous chunk of at most 8 units from the first pass to the last, so a unit's line blocks and bucket (unit_key, read back
+// by the thread that wrote them) and its source (src_key, written by the owner of the source's first unit, read behind a barrier) stay
+// in LDS, the histogram's scan and the scan of the line blocks -- which runs in unit order and does not wait for the sort -- share one
+// pass and one barrier, and a unit's record goes straight to the slot its bucket hands out: order[] and line_base[] are not written
+// (nothing but the other path reads them).  Same buckets, same line bases, same queue word and error flag as order_units; units of one
+// bucket follow each other as the LDS atomics retire, there as here.
+__device__ __forceinline__ void order_units_lds(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ recs,
+                                                long long capacity_blocks, unsigned long long* __restrict__ queue, unsigned long long queue0,
+                                                int* __restrict__ err_flag, int* hist, int* wave_tot, int* unit_key, int* src_key) {
+  const int n_units = n_src * kUnits;
+  const int per = (n_units + 1023) / 1024;
+  const int lo = (int)threadIdx.x * per, hi = lo + per < n_units ? lo + per : n_units;
+  const double inv_area = 1.0 / ((double)nx * (double)ny), inv_side = 1.0 / (double)(nx > ny ? nx : ny);
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int u = lo; u < hi; ++u) {
+    const int s = u / kUnits, qo = u - s * kUnits;
+    const int sx = src_xy[2 * s], sy = src_xy[2 * s + 1];
+    const bool inside = !(sx < 0 || sy < 0 || sx >= nx || sy >= ny);
+    int nb = 0, bucket = kBuckets - 1;
+    if (inside) {
+      UnitGeo g;
+      g.init(nx, ny, qo, sx, sy);
+      nb = g.line_blocks();
+      double cells = 0.0;
+      if (g.n_strips > 0) {
+        if (g.x_major) { const double r = g.rows_total; cells = r * g.ni - r * (r - 1) * 0.5; }
+        else { const double c = g.cols_total; cells = c * (g.nj - 1) - c * (c - 1) * 0.5; }
+      }
+      // (the key of order_units, term for term)
+      const double march = (double)(g.x_major ? g.ni : g.nj) * inv_side;
+      double f = 0.8 * march + 0.2 * (cells * inv_area * 1.6 > 1.0 ? 1.0 : cells * inv_area * 1.6);
+      if (f > 1.0) f = 1.0;
+      bucket = (kBuckets - 1) - (int)(f * (kBuckets - 1));
+    }
+    unit_key[u] = nb | (bucket << 20);
+    if (qo == 0) src_key[s] = inside ? (sx | (sy << 16)) : -1;
+    mine += nb;
+    atomicAdd(&hist[bucket], 1);
+  }
+  __syncthreads();
+  // two exclusive scans off one pass: the buckets' counts (one per thread) and the chunks' line blocks
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int count = hist[threadIdx.x];
+  int inc_h = count, inc_b = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int th = __shfl_up(inc_h, off, 64), tb = __shfl_up(inc_b, off, 64);
+    if (lane >= off) { inc_h += th; inc_b += tb; }
+  }
+  if (lane == 63) { wave_tot[wv] = inc_h; wave_tot[16 + wv] = inc_b; }
+  __syncthreads();
+  int before_h = 0, before_b = 0, total = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    before_h += k < wv ? wave_tot[k] : 0;
+    before_b += k < wv ? wave_tot[16 + k] : 0;
+    total += wave_tot[16 + k];
+  }
+  hist[threadIdx.x] = before_h + inc_h - count;  // (its own entry, which no other thread has read since the barrier before the scan)
+  __syncthreads();
+  const bool fits = (long long)total <= capacity_blocks;
+  // the records (see order_units for what they say when the lines do not fit)
+  int at = before_b + inc_b - mine;
+  for (int u = lo; u < hi; ++u) {
+    const int key = unit_key[u], nb = key & ((1 << 20) - 1);
+    const int k = atomicAdd(&hist[key >> 20], 1);
+    reinterpret_cast<int4*>(recs)[k] = make_int4(u, !fits ? -2 : src_key[u / kUnits], at, 0);
+    at += nb;
+  }
+  if (threadIdx.x == 0) {
+    *queue = fits ? queue0 : (unsigned long long)n_units;
+    if (!fits) atomicOr(err_flag, 4);
+  }
+}
+
 __global__ void __launch_bounds__(1024) vhp_pool_order(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order,
                                                        int* __restrict__ line_base, int* __restrict__ recs, long long capacity_blocks,
                                                        unsigned long long* __restrict__ queue, unsigned long long queue0,
                                                        int* __restrict__ err_flag) {
   __shared__ int hist[kBuckets];
-  __shared__ int wave_tot[16];
+  __shared__ int wave_tot[32];
   __shared__ int blocks[kOrderLdsUnits];
+  __shared__ int src_key[kOrderLdsUnits / kUnits];
   VHP_DIAG_TL_RESET
-  if (n_src * kUnits <= kOrderLdsUnits) order_units(src_xy, n_src, nx, ny, order, line_base, recs, capacity_blocks, queue, queue0, err_flag, hist, wave_tot, blocks);
+  if (n_src * kUnits <= kOrderLdsUnits) order_units_lds(src_xy, n_src, nx, ny, recs, capacity_blocks, queue, queue0, err_flag, hist, wave_tot, blocks, src_key);
   else order_units(src_xy, n_src, nx, ny, order, line_base, recs, capacity_blocks, queue, queue0, err_flag, hist, wave_tot, line_base);
 }
 
