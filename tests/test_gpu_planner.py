@@ -200,3 +200,19 @@ def test_plain_speculative_plain_on_one_context(vhp, oracle):
         spec = c.planner_solve_speculative(start, end, 0.3, 80, 4, 0)
         _assert_same_solution(spec, want, "speculative solve %d" % k)
     assert seen == {0, 1}, "pick sources that give solves of both parities (%r)" % seen
+
+    # ... and the shared state entered from the speculative side first, then across a change of grid: a fresh context solves
+    # speculative then plain on one grid, and after set_map to a smaller one speculative, plain and a batch of three
+    c = vhp.Context(0)
+    for nx, ny, seed, first in ((64, 48, 11, True), (48, 40, 12, False)):
+        occ = maps.random_rect_map(nx, ny, 6, 3, 9, 3, 9, seed)
+        pts = maps.free_sources(occ, 4, seed + 30)
+        queries = [tuple(int(v) for v in pts[k]) + tuple(int(v) for v in pts[k + 1]) for k in range(3)]
+        wants = [oracle.solve(occ, q[:2], q[2:], 0.3, 40) for q in queries]
+        c.set_map(occ)
+        what = "%dx%d after %s" % (nx, ny, "nothing" if first else "64x48")
+        _assert_same_solution(c.planner_solve_speculative(queries[0][:2], queries[0][2:], 0.3, 40, 2, 0), wants[0], what + ": speculative")
+        _assert_same_solution(c.planner_solve(queries[0][:2], queries[0][2:], 0.3, 40), wants[0], what + ": plain")
+        if not first:
+            for k, got in enumerate(c.planner_solve_batch(queries, 0.3, 40)):
+                _assert_same_solution(got, wants[k], what + ": batch query %d" % k)

@@ -499,17 +499,6 @@ int planner_batch_group_size(const vhp_ctx* c, const vhp::PackedMaps& m, uint64_
   return c->opt_planner_batch_group > 0 ? std::min(g, c->opt_planner_batch_group) : g;
 }
 
-// The batch planner's front sweep of one query (where the latency sweep does not take a single source): vhp_planner_sweep, as
-// planner_solve launches it.
-template <int R, bool MULTI>
-hipError_t launch_batch_fronts(vhp_ctx* c, const vhp::DevMap& m, const vhp::PlannerDev& d, int W) {
-  const size_t lds = vhp::sweep_lds_bytes(R, W, MULTI);
-  auto k = vhp::vhp_planner_sweep<R, MULTI>;
-  if (hipError_t e = raise_lds_limit(c, reinterpret_cast<const void*>(k), lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(4), dim3(128 * W), lds, c->stream, m, d);
-  return hipGetLastError();
-}
-
 // The batch planner's state on the single map, or with `maps` on the stack: its queries, its maps, and what a call that finds no
 // solved batch there says after its name.
 struct BatchOn {
@@ -539,6 +528,27 @@ void note_unsolved(vhp_ctx* ctx, int rc) {
     ctx->pl.path_state = 2;
     ctx->pl.last_code = rc;
   }
+}
+
+// What vhp_planner_solve and vhp_planner_solve_speculative do around their solve: the checks before it, the plan of its sweeps (n_src
+// sources per launch, n_workgroups of round scratch for the front sweep), and what the context keeps of how it ended.  solve(pm, plan,
+// &msg) sets the latency launches the plan allows on ctx->pl and runs the solve.
+template <typename Solve>
+int planner_call(vhp_ctx* ctx, const char* who, int n_src, size_t n_workgroups, Solve solve) {
+  if (!ctx) return VHP_ERR_ARG;
+  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no map set");
+  VHP_ON_DEVICE(ctx);
+  std::string msg;
+  vhp::DevMap pm = dev_map(ctx->map);
+  vhp::SweepPlan plan;
+  hipError_t eb = plan_planner(ctx, pm, n_src, n_workgroups, &plan);
+  if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+  ctx->pl.path_state = 0;
+  const int rc = solve(pm, plan, &msg);
+  note_unsolved(ctx, rc);
+  ctx->timed = true;
+  if (rc != VHP_OK) ctx->err = msg;
+  return rc;
 }
 
 // What a path call reads of the last batch on b (nx x ny): every query's slot or validation code, its n_pivots, the slots' arrays.
@@ -1239,16 +1249,8 @@ int vhp_last_elapsed_ms(vhp_ctx* ctx, float* ms) {
 int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end_y, double threshold,
                       uint64_t max_iter, uint64_t* came_from, double* vis_global, double* vis_local,
                       int32_t* pivots_xy, uint32_t* n_pivots) {
-  if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve: no map set");
-  VHP_ON_DEVICE(ctx);
-  std::string msg;
-  vhp::DevMap pm = dev_map(ctx->map);
-  {
-    // one source per sweep: the latency sweep wherever a batch of one would take it (94 against 67 us per sweep at 690^2)
-    vhp::SweepPlan plan;
-    hipError_t eb = plan_planner(ctx, pm, 1, 4, &plan);
-    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+  // one source per sweep: the latency sweep wherever a batch of one would take it (94 against 67 us per sweep at 690^2)
+  return planner_call(ctx, "vhp_planner_solve", 1, 4, [&](const vhp::DevMap& pm, const vhp::SweepPlan& plan, std::string* msg) {
     ctx->pl.lat_sweep = nullptr;
     if (plan.kernel == 4)
       ctx->pl.lat_sweep = [ctx](const int32_t* pivots, const int* nb, const int* done, const int* rec, double* out, bool dark_unwritten) {
@@ -1275,29 +1277,17 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
         l.planner_dev = &d;
         return launch_batch_sweep<double>(ctx, ctx->map, d.pivots, 1, d.vis_local, true, {ctx->opt_field_stride, false}, l);
       };
-  }
-  ctx->pl.path_state = 0;
-  int rc = vhp::planner_solve(ctx->pl, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x,
-                              end_y, threshold, max_iter, came_from, vis_global, vis_local, pivots_xy, n_pivots, &msg);
-  note_unsolved(ctx, rc);
-  ctx->timed = true;
-  if (rc != VHP_OK) ctx->err = msg;
-  return rc;
+    return vhp::planner_solve(ctx->pl, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y, threshold, max_iter,
+                              came_from, vis_global, vis_local, pivots_xy, n_pivots, msg);
+  });
 }
 
 int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end_y, double threshold, uint64_t max_iter, int k,
                                   int mode, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy,
                                   uint32_t* n_pivots, int32_t* stats) {
-  if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_speculative: no map set");
-  VHP_ON_DEVICE(ctx);
-  std::string msg;
-  vhp::DevMap pm = dev_map(ctx->map);
-  {
-    // k sources per launch: the latency sweep (8 k workgroups) wherever a batch of k would take it
-    vhp::SweepPlan plan;
-    hipError_t eb = plan_planner(ctx, pm, k, (size_t)4 * vhp::kSpecMaxK, &plan);
-    if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+  // k sources per launch: the latency sweep (8 k workgroups) wherever a batch of k would take it
+  return planner_call(ctx, "vhp_planner_solve_speculative", k, (size_t)4 * vhp::kSpecMaxK,
+                      [&](const vhp::DevMap& pm, const vhp::SweepPlan& plan, std::string* msg) {
     ctx->pl.lat_sweep_k = nullptr;
     if (plan.kernel == 4)
       ctx->pl.lat_sweep_k = [ctx](const int32_t* cand, int n, const int* slot_base, const int* run_if, const int* done, double* cache, bool dark_unwritten) {
@@ -1308,16 +1298,12 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
         l.dark_unwritten = dark_unwritten;
         return launch_batch_sweep<double>(ctx, ctx->map, cand, n, cache, true, {}, l);  // (the cache holds packed fields)
       };
-  }
-  int st[3] = {0, 0, 0};
-  ctx->pl.path_state = 0;
-  int rc = vhp::planner_solve_speculative(ctx->pl, ctx->spec, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y,
-                                          threshold, max_iter, k, mode, came_from, vis_global, vis_local, pivots_xy, n_pivots, st, &msg);
-  if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2]; }
-  note_unsolved(ctx, rc);
-  ctx->timed = true;
-  if (rc != VHP_OK) ctx->err = msg;
-  return rc;
+    int st[3] = {0, 0, 0};
+    const int rc = vhp::planner_solve_speculative(ctx->pl, ctx->spec, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y,
+                                                  threshold, max_iter, k, mode, came_from, vis_global, vis_local, pivots_xy, n_pivots, st, msg);
+    if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2]; }
+    return rc;
+  });
 }
 
 int vhp_planner_solve_device(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end_y, double threshold, uint64_t max_iter,
@@ -1377,11 +1363,15 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     const vhp::SweepPlan plan = plan_for_grid(ctx, m, 1, true);
     hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
     if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
+    // (where the latency sweep does not take a single source: vhp_planner_sweep, as planner_solve launches it)
     b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int k) {
       vhp::DevMap mk = pm;  // (map k of the stack: map 0's packed copies moved by k strides; k is 0 on the single map)
       mk.rows += (size_t)k * mk.ny * mk.wpr;
       mk.cols += (size_t)k * mk.nx * mk.wpc;
-      return vhp::with_sweep_shape(plan.R, plan.multi, [&](auto r, auto mr) { return launch_batch_fronts<r(), mr()>(ctx, mk, d, plan.W); });
+      auto raise_lds = [ctx](const void* fn, size_t bytes) { return raise_lds_limit(ctx, fn, bytes); };
+      return vhp::with_sweep_shape(plan.R, plan.multi, [&](auto r, auto mr) {
+        return vhp::launch_planner_kernel<r(), mr()>(vhp::vhp_planner_sweep<r(), mr()>, 4, plan.W, raise_lds, ctx->stream, mk, d);
+      });
     };
     ctx->last_kernel = 1;
   }

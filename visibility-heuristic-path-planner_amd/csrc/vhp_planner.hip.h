@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "vhp.h"
+#include "vhp_planner_host.hpp"
 #include "vhp_sweep.hip.h"
 #include "vhp_planner_dev.hip.h"
 
@@ -118,29 +119,21 @@ struct PlannerState {
 };
 
 inline void planner_free(PlannerState& s) {
-  if (s.vis_global) (void)hipFree(s.vis_global);
-  if (s.vis_local) (void)hipFree(s.vis_local);
-  if (s.vis_local2) (void)hipFree(s.vis_local2);
-  s.vis_local2 = s.vis_local_out = nullptr;
-  if (s.label) (void)hipFree(s.label);
-  if (s.came64) (void)hipFree(s.came64);
-  if (s.pivots) (void)hipFree(s.pivots);
-  if (s.ctl) (void)hipFree(s.ctl);
-  if (s.partial) (void)hipFree(s.partial);
-  if (s.ticket) (void)hipFree(s.ticket);
-  s.ticket = nullptr;
+  void* dev[] = {s.vis_global, s.vis_local, s.vis_local2, s.label, s.came64, s.pivots, s.ctl, s.partial, s.ticket};
+  for (void* p : dev)
+    if (p) (void)hipFree(p);
   if (s.h_ctl) (void)hipHostFree(s.h_ctl);
-  s.h_ctl = nullptr;
   for (auto& e : s.poll_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  s.cells = 0;
-  s.pivot_cap = 0;
-  s.path_state = 0;
-  s.vis_global = s.vis_local = nullptr;
+  s.vis_global = s.vis_local = s.vis_local2 = s.vis_local_out = nullptr;
   s.label = nullptr;
   s.came64 = nullptr;
   s.pivots = nullptr;
-  s.ctl = nullptr;
+  s.ctl = s.h_ctl = nullptr;
   s.partial = nullptr;
+  s.ticket = nullptr;
+  s.cells = 0;
+  s.pivot_cap = 0;
+  s.path_state = 0;
 }
 
 #define VHP_PL_HIP(call)                                                      \
@@ -152,79 +145,52 @@ inline void planner_free(PlannerState& s) {
     }                                                                         \
   } while (0)
 
-// The loop both solves run on the host: `enqueue` puts one batch of iterations on the stream (kernels of iterations past the end see
-// `done` and return at once); the control block is copied out behind every batch, and the host waits for the copy of batch n only
-// after batch n + 1 is on the stream -- the GPU does not idle while the host looks (until round 5 it did: 10-20 us per poll); the price is
-// one batch of kernels that return at once when the loop ends.  maze_6: 1.87 -> 1.71 ms per solve (batches of 4 or 16: no better).
-template <typename Enqueue>
-inline int planner_poll(PlannerState& s, hipStream_t stream, Enqueue enqueue, PlannerCtl* out, std::string* msg) {
-  if (!s.h_ctl) {
-    VHP_PL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_ctl), 2 * sizeof(PlannerCtl)));
-    for (auto& e : s.poll_ev) VHP_PL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+// The occupancy complement at the start and end points of n queries (x, y, x, y each) for planner_check_query: occ[2 q], occ[2 q + 1]
+// for query q; a query with a point out of bounds is skipped (its checks never look).  From the caller's host copy of the map if it
+// has one -- no trip to the device --, else one byte per point copied from d_occ and ONE synchronise for all of them.
+inline int planner_fetch_occupancy(const uint8_t* h_occ, const uint8_t* d_occ, int nx, int ny, hipStream_t stream, const int32_t* queries,
+                                   int n, uint8_t* occ, std::string* msg) {
+  bool copies = false;
+  for (int q = 0; q < n; ++q) {
+    const int32_t* p = queries + 4 * q;
+    if (!planner_in_bounds(nx, ny, p[0], p[1]) || !planner_in_bounds(nx, ny, p[2], p[3])) continue;
+    for (int e = 0; e < 2; ++e) {
+      const size_t k = (size_t)p[2 * e + 1] * nx + p[2 * e];
+      if (h_occ) { occ[2 * q + e] = h_occ[k]; continue; }
+      VHP_PL_HIP(hipMemcpyAsync(&occ[2 * q + e], d_occ + k, 1, hipMemcpyDeviceToHost, stream));
+      copies = true;
+    }
   }
-  auto post = [&](int slot) -> int {
-    // (on the solve's own stream: the copy on a second stream behind an event of this one measured 6 % slower)
-    VHP_PL_HIP(hipMemcpyAsync(&s.h_ctl[slot], s.ctl, sizeof(PlannerCtl), hipMemcpyDeviceToHost, stream));
-    VHP_PL_HIP(hipEventRecord(s.poll_ev[slot], stream));
-    return VHP_OK;
+  if (copies) VHP_PL_HIP(hipStreamSynchronize(stream));
+  return VHP_OK;
+}
+
+// The four validity checks of one query of the plain or speculative solve on s's map (h_occ, else d_occ).
+inline int planner_validate(const PlannerState& s, const uint8_t* d_occ, int nx, int ny, hipStream_t stream, int start_x, int start_y,
+                            int end_x, int end_y, std::string* msg) {
+  const int32_t query[4] = {start_x, start_y, end_x, end_y};
+  uint8_t occ[2] = {0, 0};
+  const int rc = planner_fetch_occupancy(s.h_occ, d_occ, nx, ny, stream, query, 1, occ, msg);
+  if (rc != VHP_OK) return rc;
+  const QueryCheck c = planner_check_query(nx, ny, start_x, start_y, end_x, end_y, occ[0], occ[1]);
+  if (c.code != VHP_OK) *msg = c.msg;
+  return c.code;
+}
+
+// The state both solves share, for a grid of `cells` and a pivot list of pivot_ints: a new cell count starts afresh, the pivot list
+// only grows, and the second local field (PlannerDev::vis_other) is allocated once, where a solve asks for it.  What a solve resets
+// is its own business.
+inline int planner_ensure_state(PlannerState& s, size_t cells, size_t pivot_ints, bool second_local, std::string* msg) {
+  auto alloc_local = [&](double** p) -> hipError_t {
+    return s.local_uncached ? hipExtMallocWithFlags(reinterpret_cast<void**>(p), cells * 8, hipDeviceMallocUncached) : hipMalloc(p, cells * 8);
   };
-  // (an error return leaves nothing in flight: kernels of this solve and a copy into h_ctl may be on the stream when a later enqueue fails)
-  auto fail = [&](int rc) -> int { (void)hipStreamSynchronize(stream); return rc; };
-  int rc = enqueue();
-  if (rc != VHP_OK) return fail(rc);
-  if ((rc = post(0)) != VHP_OK) return fail(rc);
-  for (int q = 0;; ++q) {
-    if ((rc = enqueue()) != VHP_OK) return fail(rc);
-    if ((rc = post((q + 1) & 1)) != VHP_OK) return fail(rc);
-    if (hipEventSynchronize(s.poll_ev[q & 1]) != hipSuccess) { *msg = "hipEventSynchronize (planner poll) failed"; return fail(VHP_ERR_HIP); }
-    *out = s.h_ctl[q & 1];
-    if (out->done) return VHP_OK;
-  }
-}
-
-template <int R, bool MULTI>
-inline hipError_t launch_planner_fronts(PlannerState& s, const DevMap& m, const PlannerDev& d, int W, hipStream_t stream) {
-  const size_t lds = sweep_lds_bytes(R, W, MULTI);
-  auto k = vhp_planner_sweep<R, MULTI>;
-  {
-    hipError_t e = s.raise_lds ? s.raise_lds(reinterpret_cast<const void*>(k), lds)
-                               : hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(4), dim3(128 * W), lds, stream, m, d);
-  return hipGetLastError();
-}
-
-inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ, hipStream_t stream, hipEvent_t ev0,
-                         hipEvent_t ev1, int start_x, int start_y, int end_x, int end_y, double threshold,
-                         uint64_t max_iter, uint64_t* came_from, double* vis_global, double* vis_local,
-                         int32_t* pivots_xy, uint32_t* n_pivots, std::string* msg) {
-  const int nx = m.nx, ny = m.ny;
-  // the four validity checks of solve(), in the reference's order (solver.cpp:89-116)
-  auto valid = [&](int x, int y) { return (size_t)x < (size_t)nx && (size_t)y < (size_t)ny; };
-  if (!valid(start_x, start_y)) { *msg = "Start point is out of bounds."; return VHP_ERR_START_OOB; }
-  if (!valid(end_x, end_y)) { *msg = "End point is out of bounds."; return VHP_ERR_END_OOB; }
-  uint8_t occ_s = 0, occ_e = 0;
-  if (s.h_occ) {  // (the map came from the host: its copy answers, no trip to the device)
-    occ_s = s.h_occ[(size_t)start_y * nx + start_x];
-    occ_e = s.h_occ[(size_t)end_y * nx + end_x];
-  } else {
-    VHP_PL_HIP(hipMemcpyAsync(&occ_s, d_occ + (size_t)start_y * nx + start_x, 1, hipMemcpyDeviceToHost, stream));
-    VHP_PL_HIP(hipMemcpyAsync(&occ_e, d_occ + (size_t)end_y * nx + end_x, 1, hipMemcpyDeviceToHost, stream));
-    VHP_PL_HIP(hipStreamSynchronize(stream));
-  }
-  if (!occ_s) { *msg = "Start point is not valid (occupied)"; return VHP_ERR_START_OCCUPIED; }
-  if (!occ_e) { *msg = "End point is not valid (occupied)"; return VHP_ERR_END_OCCUPIED; }
-  if (max_iter > (1u << 24)) { *msg = "max_iter too large"; return VHP_ERR_ARG; }
-
-  const size_t cells = (size_t)nx * ny;
-  const size_t pcap = 2 * (size_t)(max_iter + 2);
   if (s.cells != cells) {
     planner_free(s);
     VHP_PL_HIP(hipMalloc(&s.vis_global, cells * 8));
-    s.local_uncached = std::getenv("VHP_PLANNER_UNCACHED") != nullptr;   // (an experiment of the one-kernel iteration: vhp_capi.hip)
-    if (s.local_uncached) VHP_PL_HIP(hipExtMallocWithFlags(reinterpret_cast<void**>(&s.vis_local), cells * 8, hipDeviceMallocUncached));
-    else VHP_PL_HIP(hipMalloc(&s.vis_local, cells * 8));
+    // (an experiment of the one-kernel iteration: vhp_capi.hip; read where the local fields are allocated, so that the flag the
+    // kernels get says what the memory is whichever solve came first)
+    s.local_uncached = std::getenv("VHP_PLANNER_UNCACHED") != nullptr;
+    VHP_PL_HIP(alloc_local(&s.vis_local));
     VHP_PL_HIP(hipMalloc(&s.label, cells * 4));
     VHP_PL_HIP(hipMalloc(&s.came64, cells * 8));
     VHP_PL_HIP(hipMalloc(&s.ctl, sizeof(PlannerCtl) + 16));   // (+ the 16-byte pivot record: PlannerDev::rec)
@@ -232,33 +198,22 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
     VHP_PL_HIP(hipMalloc(&s.ticket, 2 * sizeof(unsigned int)));   // ([1]: the sweep workgroups of a one-kernel iteration that have finished)
     s.cells = cells;
   }
-  if (s.pivot_cap < pcap) {
+  if (s.pivot_cap < pivot_ints) {
     if (s.pivots) (void)hipFree(s.pivots);
     s.pivots = nullptr;
-    VHP_PL_HIP(hipMalloc(&s.pivots, pcap * sizeof(int32_t)));
-    s.pivot_cap = pcap;
+    VHP_PL_HIP(hipMalloc(&s.pivots, pivot_ints * sizeof(int32_t)));
+    s.pivot_cap = pivot_ints;
   }
-  // (the second local field only where the latency sweep runs the loop; the speculative solve, which shares this state, has one)
-  if (s.lat_sweep && !s.vis_local2) {
-    if (s.local_uncached) VHP_PL_HIP(hipExtMallocWithFlags(reinterpret_cast<void**>(&s.vis_local2), cells * 8, hipDeviceMallocUncached));
-    else VHP_PL_HIP(hipMalloc(&s.vis_local2, cells * 8));
-  }
-  // reset(): visibility_global_ = 0, visibility_ = 0, cameFrom_ = 1e15   (solver.cpp:42-47)
-  VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, cells * 8, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.vis_local, 0, cells * 8, stream));
-  if (s.vis_local2) VHP_PL_HIP(hipMemsetAsync(s.vis_local2, 0, cells * 8, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, cells * 4, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, pcap * sizeof(int32_t), stream));
-  VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, 2 * sizeof(unsigned int), stream));
+  if (second_local && !s.vis_local2) VHP_PL_HIP(alloc_local(&s.vis_local2));
+  return VHP_OK;
+}
 
+// What the kernels of a solve on s get: its arrays, the query's end point and loop condition, one local field.
+inline PlannerDev planner_dev(const PlannerState& s, int nx, int ny, double threshold, int end_x, int end_y, uint64_t max_iter) {
   PlannerDev d;
   d.vis_global = s.vis_global;
   d.vis_local = s.vis_local;
   d.vis_other = nullptr;
-  // With the latency sweep the dark part of a field -- most of it, in a maze -- is not written at all: two local fields take
-  // turns, and the epilogue that reads one clears what the sweep before last left in the other.
-  const bool two_fields = (bool)s.lat_sweep;
-  size_t launches = 0;
   d.label = s.label;
   d.pivots = s.pivots;
   d.ctl = s.ctl;
@@ -267,27 +222,143 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
   d.partial = s.partial;
   d.ticket = s.ticket;
   d.threshold = threshold;
-  {
-    volatile double q = (double)((size_t)ny * ny + (size_t)nx * nx);
-    d.scale = std::sqrt(q);  // scale_, solver.cpp:49
-  }
+  d.scale = planner_scale(nx, ny);
   d.end_x = end_x;
   d.end_y = end_y;
   d.max_iter = max_iter;
+  return d;
+}
 
+#ifndef VHP_PLANNER_BATCH
+#define VHP_PLANNER_BATCH 8
+#endif
+constexpr int kPollIterations = VHP_PLANNER_BATCH;  // iterations enqueued per host poll (those past the end see `done` and return at once)
+
+// The loop every solve runs on the host: `enqueue` puts one batch of iterations on the stream (kernels of iterations past the end see
+// `done` and return at once); a word of the loop's state (*dev: the control block, a batch's count of finished queries) is copied out
+// behind every batch, into the two pinned slots h[0], h[1] in turn with an event each, and the host waits for the copy of batch n only
+// after batch n + 1 is on the stream -- the GPU does not idle while the host looks (until round 5 it did: 10-20 us per poll); the price is
+// one batch of kernels that return at once when the loop ends.  maze_6: 1.87 -> 1.71 ms per solve (batches of 4 or 16: no better).
+// The loop ends when done(copy) holds; *out is that copy.  who: the solve's name for the poll, in its error string.
+template <typename T, typename Enqueue, typename Done>
+inline int planner_poll(hipStream_t stream, const T* dev, T* h, hipEvent_t* ev, Enqueue enqueue, Done done, const char* who, T* out,
+                        std::string* msg) {
+  auto post = [&](int slot) -> int {
+    // (on the solve's own stream: the copy on a second stream behind an event of this one measured 6 % slower)
+    VHP_PL_HIP(hipMemcpyAsync(&h[slot], dev, sizeof(T), hipMemcpyDeviceToHost, stream));
+    VHP_PL_HIP(hipEventRecord(ev[slot], stream));
+    return VHP_OK;
+  };
+  // (an error return leaves nothing in flight: kernels of this solve and a copy into h may be on the stream when a later enqueue fails)
+  auto fail = [&](int rc) -> int { (void)hipStreamSynchronize(stream); return rc; };
+  int rc = enqueue();
+  if (rc != VHP_OK) return fail(rc);
+  if ((rc = post(0)) != VHP_OK) return fail(rc);
+  for (int q = 0;; ++q) {
+    if ((rc = enqueue()) != VHP_OK) return fail(rc);
+    if ((rc = post((q + 1) & 1)) != VHP_OK) return fail(rc);
+    if (hipEventSynchronize(ev[q & 1]) != hipSuccess) { *msg = std::string("hipEventSynchronize (") + who + ") failed"; return fail(VHP_ERR_HIP); }
+    *out = h[q & 1];
+    if (done(*out)) return VHP_OK;
+  }
+}
+
+// ... of the plain and the speculative solve: on s's control block, until `done` is set (the pinned copies and their events: made by the
+// first solve)
+template <typename Enqueue>
+inline int planner_poll_ctl(PlannerState& s, hipStream_t stream, Enqueue enqueue, PlannerCtl* out, std::string* msg) {
+  if (!s.h_ctl) {
+    VHP_PL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_ctl), 2 * sizeof(PlannerCtl)));
+    for (auto& e : s.poll_ev) VHP_PL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  return planner_poll(stream, s.ctl, s.h_ctl, s.poll_ev, enqueue, [](const PlannerCtl& c) { return c.done != 0; }, "planner poll", out, msg);
+}
+
+// A sweep kernel of the planner's -- vhp_planner_sweep<R, MULTI> on `quadrants` = 4 workgroups, vhp_spec_sweep<R, MULTI> on 4 K -- in
+// the front sweep's shape: the dynamic-LDS limit raised (raise_lds: the caller's per-device bookkeeping, vhp_capi.hip), then the launch.
+template <int R, bool MULTI, typename Kernel, typename RaiseLds, typename... Args>
+inline hipError_t launch_planner_kernel(Kernel k, int quadrants, int W, const RaiseLds& raise_lds, hipStream_t stream,
+                                        const Args&... args) {
+  const size_t lds = sweep_lds_bytes(R, W, MULTI);
+  if (hipError_t e = raise_lds(reinterpret_cast<const void*>(k), lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(quadrants), dim3(128 * W), lds, stream, args...);
+  return hipGetLastError();
+}
+
+// Host copies of a solve's results, laid out as vhp_planner_solve's outputs (any may be null): the pivots 0 .. nb, the labels widened
+// to cameFrom_ through came64 (`cells` entries of device scratch, needed with came_from only), the union and the local field; one
+// synchronise at the end.  The pivots' copy goes first, as the plain solve has always posted it, or with pivots_last behind the fields',
+// as vhp_planner_batch_results has: the order of a call's stream operations stays what it was.
+inline int planner_copy_out(hipStream_t stream, size_t cells, const uint32_t* label, unsigned long long* came64, const double* vis_global_dev,
+                            const double* vis_local_dev, const int32_t* pivots_dev, uint32_t nb, uint64_t* came_from, double* vis_global,
+                            double* vis_local, int32_t* pivots_xy, std::string* msg, bool pivots_last = false) {
+  auto copy_pivots = [&]() -> int {
+    if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, pivots_dev, 2 * (size_t)(nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    return VHP_OK;
+  };
+  if (!pivots_last)
+    if (const int rc = copy_pivots(); rc != VHP_OK) return rc;
+  if (came_from) {
+    hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, label, came64, cells);
+    VHP_PL_HIP(hipGetLastError());
+    VHP_PL_HIP(hipMemcpyAsync(came_from, came64, cells * 8, hipMemcpyDeviceToHost, stream));
+  }
+  if (vis_global) VHP_PL_HIP(hipMemcpyAsync(vis_global, vis_global_dev, cells * 8, hipMemcpyDeviceToHost, stream));
+  if (vis_local) VHP_PL_HIP(hipMemcpyAsync(vis_local, vis_local_dev, cells * 8, hipMemcpyDeviceToHost, stream));
+  if (pivots_last)
+    if (const int rc = copy_pivots(); rc != VHP_OK) return rc;
+  VHP_PL_HIP(hipStreamSynchronize(stream));
+  return VHP_OK;
+}
+
+// What a solve on s leaves when its loop has ended with `ctl`: the bookkeeping the path calls read (PlannerState::path_state) and the
+// host copies of its results (the local field: s.vis_local_out).
+inline int planner_finish(PlannerState& s, hipStream_t stream, const PlannerCtl& ctl, int end_x, int end_y, uint64_t* came_from,
+                          double* vis_global, double* vis_local, int32_t* pivots_xy, uint32_t* n_pivots, std::string* msg) {
+  const uint32_t nb = (uint32_t)ctl.nb;
+  if (n_pivots) *n_pivots = nb;
+  s.path_state = 1;
+  s.last_nb = nb;
+  s.last_end_x = end_x;
+  s.last_end_y = end_y;
+  return planner_copy_out(stream, s.cells, s.label, s.came64, s.vis_global, s.vis_local_out, s.pivots, nb, came_from, vis_global, vis_local,
+                          pivots_xy, msg);
+}
+
+inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ, hipStream_t stream, hipEvent_t ev0,
+                         hipEvent_t ev1, int start_x, int start_y, int end_x, int end_y, double threshold,
+                         uint64_t max_iter, uint64_t* came_from, double* vis_global, double* vis_local,
+                         int32_t* pivots_xy, uint32_t* n_pivots, std::string* msg) {
+  const int nx = m.nx, ny = m.ny;
+  if (const int rc = planner_validate(s, d_occ, nx, ny, stream, start_x, start_y, end_x, end_y, msg); rc != VHP_OK) return rc;
+  if (max_iter > (1u << 24)) { *msg = "max_iter too large"; return VHP_ERR_ARG; }
+
+  const size_t cells = (size_t)nx * ny;
+  const size_t pcap = planner_pivot_ints(max_iter);
+  // With the latency sweep the dark part of a field -- most of it, in a maze -- is not written at all: two local fields take
+  // turns, and the epilogue that reads one clears what the sweep before last left in the other.
+  // (the second local field only where the latency sweep runs the loop; the speculative solve, which shares this state, has one)
+  const bool two_fields = (bool)s.lat_sweep;
+  if (const int rc = planner_ensure_state(s, cells, pcap, two_fields, msg); rc != VHP_OK) return rc;
+  // reset(): visibility_global_ = 0, visibility_ = 0, cameFrom_ = 1e15   (solver.cpp:42-47)
+  VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, cells * 8, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.vis_local, 0, cells * 8, stream));
+  if (s.vis_local2) VHP_PL_HIP(hipMemsetAsync(s.vis_local2, 0, cells * 8, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, cells * 4, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, pcap * sizeof(int32_t), stream));
+  VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, 2 * sizeof(unsigned int), stream));
+
+  PlannerDev d = planner_dev(s, nx, ny, threshold, end_x, end_y, max_iter);
+  size_t launches = 0;
   const int R = s.R, W = s.W;
   const bool multi = s.multi;
   VHP_PL_HIP(hipEventRecord(ev0, stream));
   hipLaunchKernelGGL(vhp_planner_init, dim3(1), dim3(64), 0, stream, d, nx, start_x, start_y);
   VHP_PL_HIP(hipGetLastError());
   PlannerCtl ctl{};
-#ifndef VHP_PLANNER_BATCH
-#define VHP_PLANNER_BATCH 8
-#endif
-  const int batch = VHP_PLANNER_BATCH;  // iterations enqueued per host poll (those past the end see `done` and return at once)
   {
-    const int rc = planner_poll(s, stream, [&]() -> int {
-      for (int b = 0; b < batch; ++b, ++launches) {
+    const int rc = planner_poll_ctl(s, stream, [&]() -> int {
+      for (int b = 0; b < kPollIterations; ++b, ++launches) {
         if (two_fields) {
           d.vis_local = (launches & 1) ? s.vis_local2 : s.vis_local;
           d.vis_other = (launches & 1) ? s.vis_local : s.vis_local2;
@@ -298,7 +369,9 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
           continue;
         }
         hipError_t e = s.lat_sweep ? s.lat_sweep(d.pivots, &s.ctl->nb, &s.ctl->done, d.rec, d.vis_local, true)
-                                   : with_sweep_shape(R, multi, [&](auto r, auto mr) { return launch_planner_fronts<r(), mr()>(s, m, d, W, stream); });
+                                   : with_sweep_shape(R, multi, [&](auto r, auto mr) {
+                                       return launch_planner_kernel<r(), mr()>(vhp_planner_sweep<r(), mr()>, 4, W, s.raise_lds, stream, m, d);
+                                     });
         if (e != hipSuccess) { *msg = std::string("planner launch: ") + hipGetErrorString(e); return VHP_ERR_HIP; }
         hipLaunchKernelGGL(vhp_planner_epilogue, dim3(kEpilogueBlocks), dim3(kEpilogueThreads), 0, stream, m, d);
         VHP_PL_HIP(hipGetLastError());
@@ -311,23 +384,8 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
 
   // (launch number n is iteration number n while the loop runs; the last iteration that ran is number iters - 1)
   s.vis_local_out = (two_fields && ctl.iters > 0 && ((ctl.iters - 1) & 1)) ? s.vis_local2 : s.vis_local;
-  const uint32_t nb = (uint32_t)ctl.nb;
-  if (n_pivots) *n_pivots = nb;
-  s.path_state = 1;
-  s.last_nb = nb;
-  s.last_end_x = end_x;
-  s.last_end_y = end_y;
-  if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, s.pivots, 2 * (size_t)(nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  if (came_from) {
-    hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, s.label, s.came64, cells);
-    VHP_PL_HIP(hipGetLastError());
-    VHP_PL_HIP(hipMemcpyAsync(came_from, s.came64, cells * 8, hipMemcpyDeviceToHost, stream));
-  }
-  if (vis_global) VHP_PL_HIP(hipMemcpyAsync(vis_global, s.vis_global, cells * 8, hipMemcpyDeviceToHost, stream));
-  if (vis_local) VHP_PL_HIP(hipMemcpyAsync(vis_local, s.vis_local_out, cells * 8, hipMemcpyDeviceToHost, stream));
-  VHP_PL_HIP(hipStreamSynchronize(stream));
-  if (ctl.status == VHP_ERR_MAX_ITER) *msg = "Max iters hit. Solution could not be found. Try lowering visibility threshold.";
-  if (ctl.status == VHP_ERR_NOTHING_LIT) *msg = "no cell reached the visibility threshold";
+  if (const int rc = planner_finish(s, stream, ctl, end_x, end_y, came_from, vis_global, vis_local, pivots_xy, n_pivots, msg); rc != VHP_OK) return rc;
+  if (const char* why = planner_status_message(ctl.status)) *msg = why;
   return ctl.status;
 }
 
@@ -741,94 +799,34 @@ inline void spec_free(SpecState& s) {
   s.cells = 0;
 }
 
-template <int R, bool MULTI>
-inline hipError_t launch_spec_fronts(PlannerState& s, const DevMap& m, const PlannerDev& d, const SpecDev& sp, int W, hipStream_t stream) {
-  const size_t lds = sweep_lds_bytes(R, W, MULTI);
-  auto k = vhp_spec_sweep<R, MULTI>;
-  {
-    hipError_t e = s.raise_lds ? s.raise_lds(reinterpret_cast<const void*>(k), lds)
-                               : hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(4 * sp.K), dim3(128 * W), lds, stream, m, d, sp);
-  return hipGetLastError();
-}
-
 // The loop of planner_solve with the speculative sweep launches.  stats (3 ints, may be null): iterations whose pivot was
-// cached, iterations that swept, fields swept.  The caller has validated start / end and sized the round scratch for 4 K units.
+// cached, iterations that swept, fields swept.  Validates start / end itself, like planner_solve; the caller has sized the round
+// scratch for 4 K units.
 inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMap& m, const uint8_t* d_occ, hipStream_t stream, hipEvent_t ev0,
                                      hipEvent_t ev1, int start_x, int start_y, int end_x, int end_y, double threshold, uint64_t max_iter, int K,
                                      int mode, uint64_t* came_from, double* vis_global, double* vis_local, int32_t* pivots_xy,
                                      uint32_t* n_pivots, int* stats, std::string* msg) {
   const int nx = m.nx, ny = m.ny;
-  // the four validity checks of solve(), in the reference's order (solver.cpp:89-116)
-  auto valid = [&](int x, int y) { return (size_t)x < (size_t)nx && (size_t)y < (size_t)ny; };
-  if (!valid(start_x, start_y)) { *msg = "Start point is out of bounds."; return VHP_ERR_START_OOB; }
-  if (!valid(end_x, end_y)) { *msg = "End point is out of bounds."; return VHP_ERR_END_OOB; }
-  uint8_t occ_s = 0, occ_e = 0;
-  if (s.h_occ) {  // (the map came from the host: its copy answers, no trip to the device)
-    occ_s = s.h_occ[(size_t)start_y * nx + start_x];
-    occ_e = s.h_occ[(size_t)end_y * nx + end_x];
-  } else {
-    VHP_PL_HIP(hipMemcpyAsync(&occ_s, d_occ + (size_t)start_y * nx + start_x, 1, hipMemcpyDeviceToHost, stream));
-    VHP_PL_HIP(hipMemcpyAsync(&occ_e, d_occ + (size_t)end_y * nx + end_x, 1, hipMemcpyDeviceToHost, stream));
-    VHP_PL_HIP(hipStreamSynchronize(stream));
-  }
-  if (!occ_s) { *msg = "Start point is not valid (occupied)"; return VHP_ERR_START_OCCUPIED; }
-  if (!occ_e) { *msg = "End point is not valid (occupied)"; return VHP_ERR_END_OCCUPIED; }
+  if (const int rc = planner_validate(s, d_occ, nx, ny, stream, start_x, start_y, end_x, end_y, msg); rc != VHP_OK) return rc;
   if (max_iter > (1u << 24)) { *msg = "max_iter too large"; return VHP_ERR_ARG; }
   if ((K != 1 && K != 2 && K != 4 && K != 8) || (mode != 0 && mode != 1)) { *msg = "speculative planner: k must be 1, 2, 4 or 8 and mode 0 or 1"; return VHP_ERR_ARG; }
   const size_t cells = (size_t)nx * ny;
-  const size_t pcap = 2 * (size_t)(max_iter + 2 + kSpecMaxK);
-  if (s.cells != cells) {
-    planner_free(s);
-    VHP_PL_HIP(hipMalloc(&s.vis_global, cells * 8));
-    VHP_PL_HIP(hipMalloc(&s.vis_local, cells * 8));
-    VHP_PL_HIP(hipMalloc(&s.label, cells * 4));
-    VHP_PL_HIP(hipMalloc(&s.came64, cells * 8));
-    VHP_PL_HIP(hipMalloc(&s.ctl, sizeof(PlannerCtl) + 16));   // (+ the 16-byte pivot record: PlannerDev::rec)
-    VHP_PL_HIP(hipMalloc(&s.partial, kSpecPartials * sizeof(PlannerKey)));
-    VHP_PL_HIP(hipMalloc(&s.ticket, 2 * sizeof(unsigned int)));   // ([1]: the sweep workgroups of a one-kernel iteration that have finished)
-    s.cells = cells;
-  }
-  if (s.pivot_cap < pcap) {
-    if (s.pivots) (void)hipFree(s.pivots);
-    s.pivots = nullptr;
-    VHP_PL_HIP(hipMalloc(&s.pivots, pcap * sizeof(int32_t)));
-    s.pivot_cap = pcap;
-  }
+  if (const int rc = planner_ensure_state(s, cells, planner_pivot_ints(max_iter, kSpecMaxK), false, msg); rc != VHP_OK) return rc;
   if (ss.cells != cells) {
     spec_free(ss);
     VHP_PL_HIP(hipMalloc(&ss.cache, (size_t)kSpecSlots * cells * 8));
     VHP_PL_HIP(hipMalloc(&ss.sc, sizeof(SpecCtl)));
     ss.cells = cells;
   }
+  // (not vis_local: vhp_spec_export_local writes all of it)
   VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, cells * 8, stream));
   VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, cells * 4, stream));
   VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, s.pivot_cap * sizeof(int32_t), stream));
   VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, 2 * sizeof(unsigned int), stream));
   if (mode == 1) VHP_PL_HIP(hipMemsetAsync(ss.cache, 0, (size_t)2 * K * cells * 8, stream));  // (the two groups of k slots that take turns: vhp_spec_epilogue)
 
-  PlannerDev d;
-  d.vis_global = s.vis_global;
-  d.vis_local = s.vis_local;
-  d.vis_other = nullptr;
+  const PlannerDev d = planner_dev(s, nx, ny, threshold, end_x, end_y, max_iter);
   s.vis_local_out = s.vis_local;
-  d.label = s.label;
-  d.pivots = s.pivots;
-  d.ctl = s.ctl;
-  d.rec = reinterpret_cast<int*>(s.ctl + 1);
-  d.local_uncached = s.local_uncached ? 1 : 0;
-  d.partial = s.partial;
-  d.ticket = s.ticket;
-  d.threshold = threshold;
-  {
-    volatile double q = (double)((size_t)ny * ny + (size_t)nx * nx);
-    d.scale = std::sqrt(q);  // scale_, solver.cpp:49
-  }
-  d.end_x = end_x;
-  d.end_y = end_y;
-  d.max_iter = max_iter;
   SpecDev sp;
   sp.sc = ss.sc;
   sp.cache = ss.cache;
@@ -843,12 +841,13 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
   hipLaunchKernelGGL(vhp_spec_init, dim3(1), dim3(64), 0, stream, d, sp, start_x, start_y);
   VHP_PL_HIP(hipGetLastError());
   PlannerCtl ctl{};
-  const int batch = VHP_PLANNER_BATCH;
   {
-    const int rc = planner_poll(s, stream, [&]() -> int {
-      for (int b = 0; b < batch; ++b) {
+    const int rc = planner_poll_ctl(s, stream, [&]() -> int {
+      for (int b = 0; b < kPollIterations; ++b) {
         hipError_t e = s.lat_sweep_k ? s.lat_sweep_k(ss.sc->cand, K, &ss.sc->cur_slot, &ss.sc->sweep, &s.ctl->done, ss.cache, mode == 1)
-                                     : with_sweep_shape(R, multi, [&](auto r, auto mr) { return launch_spec_fronts<r(), mr()>(s, m, d, sp, W, stream); });
+                                     : with_sweep_shape(R, multi, [&](auto r, auto mr) {
+                                         return launch_planner_kernel<r(), mr()>(vhp_spec_sweep<r(), mr()>, 4 * K, W, s.raise_lds, stream, m, d, sp);
+                                       });
         if (e != hipSuccess) { *msg = std::string("speculative planner launch: ") + hipGetErrorString(e); return VHP_ERR_HIP; }
         auto epi = mode == 0 ? vhp_spec_epilogue<1, false> : K == 1 ? vhp_spec_epilogue<1, true> : K == 2 ? vhp_spec_epilogue<2, true>
                            : K == 4 ? vhp_spec_epilogue<4, true> : vhp_spec_epilogue<8, true>;
@@ -865,28 +864,13 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
   SpecCtl hc{};
   VHP_PL_HIP(hipMemcpyAsync(&hc, ss.sc, sizeof(hc), hipMemcpyDeviceToHost, stream));
 
-  const uint32_t nb = (uint32_t)ctl.nb;
-  if (n_pivots) *n_pivots = nb;
-  s.path_state = 1;
-  s.last_nb = nb;
-  s.last_end_x = end_x;
-  s.last_end_y = end_y;
-  if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, s.pivots, 2 * (size_t)(nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  if (came_from) {
-    hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, s.label, s.came64, cells);
-    VHP_PL_HIP(hipGetLastError());
-    VHP_PL_HIP(hipMemcpyAsync(came_from, s.came64, cells * 8, hipMemcpyDeviceToHost, stream));
-  }
-  if (vis_global) VHP_PL_HIP(hipMemcpyAsync(vis_global, s.vis_global, cells * 8, hipMemcpyDeviceToHost, stream));
-  if (vis_local) VHP_PL_HIP(hipMemcpyAsync(vis_local, s.vis_local, cells * 8, hipMemcpyDeviceToHost, stream));
-  VHP_PL_HIP(hipStreamSynchronize(stream));
+  if (const int rc = planner_finish(s, stream, ctl, end_x, end_y, came_from, vis_global, vis_local, pivots_xy, n_pivots, msg); rc != VHP_OK) return rc;
   if (stats) { stats[0] = hc.hits; stats[1] = hc.misses; stats[2] = hc.fields_swept; }
 #ifdef VHP_DIAG_SPEC_TAIL
   fprintf(stderr, "spec tail (us, summed over the solve): start->last %.1f  gather %.1f  loads %.1f  rounds %.1f  pick %.1f\n", hc.tail_t[1] / 100.0,
           hc.tail_t[2] / 100.0, hc.tail_t[3] / 100.0, hc.tail_t[4] / 100.0, hc.tail_t[5] / 100.0);
 #endif
-  if (ctl.status == VHP_ERR_MAX_ITER) *msg = "Max iters hit. Solution could not be found. Try lowering visibility threshold.";
-  if (ctl.status == VHP_ERR_NOTHING_LIT) *msg = "no cell reached the visibility threshold";
+  if (const char* why = planner_status_message(ctl.status)) *msg = why;
   return ctl.status;
 }
 

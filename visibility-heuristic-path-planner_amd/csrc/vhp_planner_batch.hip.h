@@ -14,7 +14,7 @@
 // query that still runs: the turn is global, and a query's last local field is the one of launch iters - 1.  Each query therefore
 // computes exactly what planner_solve computes for it alone: the same sweep of the same pivot, the same epilogue body over the same
 // state.
-// The host enqueues 8 iterations per poll of the done word; the batch runs as groups of at most G queries, one after the other
+// The host enqueues kPollIterations iterations per poll of the done word (planner_poll); the batch runs as groups of at most G queries, one after the other
 // (planner_batch_group_size in vhp_capi.hip).  Where even one source does not take the latency sweep, the groups are single queries and
 // their sweep is the planner's front sweep (vhp_planner_sweep), one local field.
 // The same loop serves a stack of maps (vhp_planner_solve_maps_batch, BatchStack): every slot also has its map index, uploaded with the
@@ -174,7 +174,7 @@ struct BatchState {
   int group = 0;                          // G of the last batch
   // set by the caller: the latency sweep of n sources cand[0 .. n) into fields out, out + cells, ... (LatArgs::slot_base: x < 0 sweeps
   // nothing, dark cells unwritten), source g on map map_idx[g] (device; null: one map) -- or null: the front sweep of query d on map
-  // `map` (host; 0 on one map) (launch_planner_fronts' kernel, shape R, W, multi)
+  // `map` (host; 0 on one map) (vhp_planner_sweep through launch_planner_kernel, shape R, W, multi)
   std::function<hipError_t(const int32_t* cand, const int32_t* map_idx, int n, double* out)> lat_sweep;
   std::function<hipError_t(const PlannerDev& d, int map)> front_sweep;
 };
@@ -225,14 +225,13 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   s.codes.assign(n_queries, VHP_OK);
   // the four validity checks of solve() per query, in the reference's order (solver.cpp:89-116); the occupancy of a device map is
   // fetched for all queries at once
-  auto valid = [&](int x, int y) { return (size_t)x < (size_t)nx && (size_t)y < (size_t)ny; };
   std::vector<uint8_t> occ(2 * (size_t)n_queries, 1);
   if (stack) {  // (the bits of each query's own map, gathered on the device: one launch, one copy)
     std::vector<int4> pts;
     std::vector<int> at;   // the entry of occ that point i answers
     for (int q = 0; q < n_queries; ++q) {
       const int32_t* p = queries + 4 * q;
-      if (!valid(p[0], p[1]) || !valid(p[2], p[3])) continue;
+      if (!planner_in_bounds(nx, ny, p[0], p[1]) || !planner_in_bounds(nx, ny, p[2], p[3])) continue;
       for (int e = 0; e < 2; ++e) {
         pts.push_back(make_int4(p[2 * e], p[2 * e + 1], stack->map_idx[q], 0));
         at.push_back(2 * q + e);
@@ -251,34 +250,20 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
       VHP_PL_HIP(hipStreamSynchronize(stream));
       for (int i = 0; i < n; ++i) occ[at[i]] = bits[i];
     }
-  } else {
-    for (int q = 0; q < n_queries; ++q) {
-      const int32_t* p = queries + 4 * q;
-      if (!valid(p[0], p[1]) || !valid(p[2], p[3])) continue;
-      for (int e = 0; e < 2; ++e) {
-        const size_t k = (size_t)p[2 * e + 1] * nx + p[2 * e];
-        if (h_occ) occ[2 * q + e] = h_occ[k];
-        else VHP_PL_HIP(hipMemcpyAsync(&occ[2 * q + e], d_occ + k, 1, hipMemcpyDeviceToHost, stream));
-      }
-    }
-    if (!h_occ) VHP_PL_HIP(hipStreamSynchronize(stream));
+  } else if (const int rc = planner_fetch_occupancy(h_occ, d_occ, nx, ny, stream, queries, n_queries, occ.data(), msg); rc != VHP_OK) {
+    return rc;
   }
   std::vector<BatchQuery> run;
   std::vector<int32_t> run_map;   // (a stack: the map of each slot)
   std::string first_msg;
   for (int q = 0; q < n_queries; ++q) {
     const int32_t* p = queries + 4 * q;
-    int st = VHP_OK;
-    const char* why = nullptr;
-    if (!valid(p[0], p[1])) { st = VHP_ERR_START_OOB; why = "Start point is out of bounds."; }
-    else if (!valid(p[2], p[3])) { st = VHP_ERR_END_OOB; why = "End point is out of bounds."; }
-    else if (!occ[2 * q]) { st = VHP_ERR_START_OCCUPIED; why = "Start point is not valid (occupied)"; }
-    else if (!occ[2 * q + 1]) { st = VHP_ERR_END_OCCUPIED; why = "End point is not valid (occupied)"; }
-    status[q] = st;
+    const QueryCheck c = planner_check_query(nx, ny, p[0], p[1], p[2], p[3], occ[2 * q], occ[2 * q + 1]);
+    status[q] = c.code;
     n_pivots[q] = 0;
-    s.codes[q] = st;
-    if (why) {
-      if (first_msg.empty()) first_msg = "query " + std::to_string(q) + ": " + why;
+    s.codes[q] = c.code;
+    if (c.code != VHP_OK) {
+      if (first_msg.empty()) first_msg = "query " + std::to_string(q) + ": " + c.msg;
       continue;
     }
     s.slot_of[q] = (int)run.size();
@@ -286,7 +271,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     run_map.push_back(stack ? stack->map_idx[q] : 0);
   }
   const size_t n_run = run.size();
-  const size_t pstride = 2 * (size_t)(max_iter + 2);
+  const size_t pstride = planner_pivot_ints(max_iter);
   const bool two_fields = (bool)s.lat_sweep;
   if (!s.lat_sweep) group = 1;
   // (re)allocation: grow-only in queries and pivots; a new grid starts afresh
@@ -344,13 +329,8 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   all.n_done = s.n_done;
   all.cells = cells;
   all.pivot_stride = s.pivot_stride;
-  {
-    volatile double q = (double)((size_t)ny * ny + (size_t)nx * nx);
-    all.scale = std::sqrt(q);  // scale_, solver.cpp:49
-  }
+  all.scale = planner_scale(nx, ny);
   all.max_iter = max_iter;
-  // (an error return leaves nothing in flight)
-  auto fail = [&](int rc) -> int { (void)hipStreamSynchronize(stream); return rc; };
   for (size_t g0 = 0; g0 < n_run; g0 += (size_t)group) {
     const int n = (int)std::min((size_t)group, n_run - g0);
     // the group's view: slot g0 + g is its query g
@@ -372,7 +352,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     const int blocks = batch_epilogue_blocks(n);
     size_t launches = 0;
     auto enqueue = [&]() -> int {
-      for (int k = 0; k < 8; ++k, ++launches) {   // (iterations past a query's end see its candidate x = -1 and return at once)
+      for (int k = 0; k < kPollIterations; ++k, ++launches) {   // (iterations past a query's end see its candidate x = -1 and return at once)
         const int parity = (int)(launches & 1);
         hipError_t e = hipSuccess;
         if (s.lat_sweep) {
@@ -386,21 +366,11 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
       }
       return VHP_OK;
     };
-    // the polls of planner_poll: the done word is copied out behind every 8 iterations, and the host waits for copy n only after
-    // iterations 8 (n + 1) .. are on the stream
-    auto post = [&](int slot) -> int {
-      VHP_PL_HIP(hipMemcpyAsync(&s.h_done[slot], s.n_done, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-      VHP_PL_HIP(hipEventRecord(s.poll_ev[slot], stream));
-      return VHP_OK;
-    };
-    int rc = enqueue();
-    if (rc == VHP_OK) rc = post(0);
-    for (int p = 0; rc == VHP_OK; ++p) {
-      if ((rc = enqueue()) != VHP_OK || (rc = post((p + 1) & 1)) != VHP_OK) break;
-      if (hipEventSynchronize(s.poll_ev[p & 1]) != hipSuccess) { *msg = "hipEventSynchronize (batch planner poll) failed"; rc = VHP_ERR_HIP; break; }
-      if (s.h_done[p & 1] >= (unsigned)n) break;
-    }
-    if (rc != VHP_OK) return fail(rc);
+    // (the group's loop ends when the done word counts all its queries)
+    unsigned int n_done = 0;
+    const int rc = planner_poll(stream, s.n_done, s.h_done, s.poll_ev, enqueue, [n](unsigned int done) { return done >= (unsigned)n; },
+                                "batch planner poll", &n_done, msg);
+    if (rc != VHP_OK) return rc;
   }
   VHP_PL_HIP(hipEventRecord(ev1, stream));
   if (n_run > 0) VHP_PL_HIP(hipMemcpyAsync(s.h_ctl.data(), s.ctl, n_run * sizeof(BatchCtl), hipMemcpyDeviceToHost, stream));
@@ -435,18 +405,9 @@ inline int batch_results_host(BatchState& s, int k, hipStream_t stream, uint64_t
   const double *vg, *vl;
   const int32_t* piv;
   batch_results_device(s, k, &lab, &vg, &vl, &piv);
-  const size_t cells = s.cells;
-  if (came_from) {
-    if (!s.came64) VHP_PL_HIP(hipMalloc(&s.came64, cells * 8));
-    hipLaunchKernelGGL(vhp_labels_to_u64, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, lab, s.came64, cells);
-    VHP_PL_HIP(hipGetLastError());
-    VHP_PL_HIP(hipMemcpyAsync(came_from, s.came64, cells * 8, hipMemcpyDeviceToHost, stream));
-  }
-  if (vis_global) VHP_PL_HIP(hipMemcpyAsync(vis_global, vg, cells * 8, hipMemcpyDeviceToHost, stream));
-  if (vis_local) VHP_PL_HIP(hipMemcpyAsync(vis_local, vl, cells * 8, hipMemcpyDeviceToHost, stream));
-  if (pivots_xy) VHP_PL_HIP(hipMemcpyAsync(pivots_xy, piv, 2 * (size_t)(s.h_ctl[k].ctl.nb + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  VHP_PL_HIP(hipStreamSynchronize(stream));
-  return VHP_OK;
+  if (came_from && !s.came64) VHP_PL_HIP(hipMalloc(&s.came64, s.cells * 8));
+  return planner_copy_out(stream, s.cells, lab, s.came64, vg, vl, piv, (uint32_t)s.h_ctl[k].ctl.nb, came_from, vis_global, vis_local, pivots_xy, msg,
+                          true);
 }
 
 }  // namespace vhp
