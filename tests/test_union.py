@@ -9,28 +9,7 @@ import numpy as np
 import pytest
 
 import maps
-
-
-def _numpy_union(fields, first_index):
-    """(best, arg): sequential max-union, replace on strict improvement only"""
-    best = np.full(fields.shape[1:], -1.0, fields.dtype)
-    arg = np.full(fields.shape[1:], 0x7fffffff, np.int32)
-    for k in range(fields.shape[0]):
-        better = fields[k] > best
-        best = np.where(better, fields[k], best)
-        arg = np.where(better, np.int32(first_index + k), arg)
-    return best, arg
-
-
-def _tied_fields(rng, n, ny, nx, dtype):
-    """random fields in [0, 1] with many exact ties: values from a small set, whole fields repeated, zeros"""
-    f = rng.choice(np.array([0.0, 0.25, 0.5, 0.75, 1.0]), size=(n, ny, nx)).astype(dtype)
-    f += (rng.rand(n, ny, nx) < 0.3) * rng.rand(n, ny, nx).astype(dtype) * 0.1
-    if n > 3:
-        f[3] = f[1]          # two equal fields: every cell a tie between sources 1 and 3
-        f[n - 1] = f[0]
-    f[:, : ny // 4] = 0.0    # a region where every source is dark: the lowest index wins
-    return np.ascontiguousarray(f.astype(dtype))
+from side_kernel_shapes import _numpy_union, _tied_fields
 
 
 def test_union_shim_matches_numpy():
