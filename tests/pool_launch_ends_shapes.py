@@ -1,6 +1,7 @@
 """The batches of tests/test_gpu_pool_launch_ends.py and tests/test_pool_sim_launch_ends.py: the smallest at which the two ends of a
 pool-sweep launch -- the order pre-kernel's records and the sweep kernel's first round -- take each of their paths on a 256-CU device
-with three contexts per workgroup (the static round is on from 8 * n_sources = 3 * 256 units)."""
+with three contexts per workgroup (the static round is on from 8 * n_sources = 3 * 256 units).  tests/test_launch_plans.py asks the
+launcher's own plan (csrc/vhp_launch_plan.hpp plan_pool) whether each shape takes the path its comment claims."""
 import numpy as np
 
 import maps

@@ -24,7 +24,8 @@
 #include <memory>
 #include <vector>
 
-#include "../../visibility-heuristic-path-planner_amd/csrc/vhp_band.hpp"
+#include "../../visibility-heuristic-path-planner_amd/csrc/vhp_launch_plan.hpp"
+#include "../../visibility-heuristic-path-planner_amd/csrc/vhp_pool_scratch.hpp"
 
 using namespace vhp::pool;
 
@@ -119,7 +120,8 @@ int run_batch_t(const uint8_t* occ, int nx, int ny, const int32_t* src, int n_sr
   build_map(occ, nx, ny, h);
   const Layout L = make_layout(W, C, nx, ny, ANYW ? kTStrideAny : kTStride);
   const int n_units = n_src * kUnits;
-  // launch order: by cell count, largest first, as vhp_pool_order does (policy & 32: shuffled instead -- the result must not depend on it)
+  // launch order: by cell count, largest first -- the simulator's own order, not vhp_pool_order's (that one goes by the length of the
+  // march, unit_launch_bucket); policy & 32: shuffled instead -- the result must not depend on the order
   std::vector<int> order(n_units), line_base(n_units, 0);
   std::vector<double> weight(n_units, -1.0);
   long long line_blocks = 0;
@@ -146,7 +148,7 @@ int run_batch_t(const uint8_t* occ, int nx, int ny, const int32_t* src, int n_sr
   }
   unsigned long long queue = 0;
   int err = 0;
-  const int dstride = ((nx < ny ? nx : ny) + 64 + 15) & ~15;
+  const int dstride = vhp::diag_stride_of(nx, ny);
   std::vector<double> diag((size_t)n_src * 4 * dstride, std::numeric_limits<double>::quiet_NaN());
   Args<OutT> a;
   a.m = h.m;
@@ -171,11 +173,11 @@ int run_batch_t(const uint8_t* occ, int nx, int ny, const int32_t* src, int n_sr
   a.late_after = n_units / 2;  // one to three contexts pull from the head of the queue
   a.claim_ahead = (int)((seed * 7) % 5) * 8;   // 0, 8 .. 32 steps: a strip claimed before the strip below has reached its first window
   a.busy_cap = (policy & 64) ? 2 : W;   // policy & 64: a tight cap on the wavefronts that may sweep while units are installed
-  // the first unit of every context by workgroup index wherever the launcher would do so (vhp_pool.hip launch_pool_t), in two runs of three
+  // the first unit of every context by workgroup index wherever the launcher would do so (vhp_launch_plan.hpp plan_pool), in two runs of three
   a.n_groups = G;
-  a.static_round = (seed % 3) != 2 && a.early_ctx >= C && n_units >= C * G;
+  a.static_round = vhp::pool_static_round_ok((seed % 3) != 2, a.early_ctx, C, n_units, G);
   a.static_snake = (seed & 2) != 0;
-  if (a.static_round) queue = (unsigned long long)(a.n_head * G) | ((unsigned long long)((C - a.n_head) * G) << 32);
+  if (a.static_round) queue = vhp::pool_queue0(a.n_head, C, G);
 
   std::vector<std::vector<double>> lds(G, std::vector<double>(L.total, std::numeric_limits<double>::quiet_NaN()));
   std::vector<Worker<OutT, ANYW>> workers((size_t)G * W);

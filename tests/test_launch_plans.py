@@ -1,0 +1,301 @@
+"""How the pool sweep and the latency sweep are launched (csrc/vhp_launch_plan.hpp plan_pool, plan_lat) over a grid of launches, against
+tests/golden/launch_plans.json.
+
+CPU only: the header is host code, compiled here with the host C++ compiler and -DVHP_SIM into a small driver
+(tests/launch_plan_driver.cpp), once plain and once under the address and undefined-behaviour sanitizers.
+
+The pool sweep's grid: the sides at which the number of contexts changes (1024 / 1025, 1664 / 1665) and one either side; the largest
+sides at which 16, 3, 2 and 1 contexts still fit the LDS and the next side that asks for more (LDS_EDGES; plan_pool itself knows no
+largest side, so they lie beyond what pool_supported takes -- found with the driver: `--edges` bisects, for every number of contexts
+asked for and both builds, for the largest side that keeps it, and test_the_lds_edges_are_where_the_grid_says holds them); widths that
+are and are not a multiple of 8, both with the build for any width; batch sizes at the edge of the static round (contexts x CUs units)
+and one either side, for 256, 80 and 304 CUs; every PoolOpts key at its lowest and highest accepted value, pool_static_round at 0, 1 and
+2, pool_early_ctx below the number of contexts.
+The latency sweep's: the sides at which the workgroups per unit change and one beyond, 1 .. 64 sources (and 255 .. 257: 2048 units, what
+vhp_lat_order sorts, and the first batch beyond), every number of workgroups that can be asked for, the three CU counts, each LatFlags
+bit alone and beside d_lat_order, both pitches.
+
+Beside the table, the rows of EXPECT_POOL and EXPECT_LAT are literals derived by hand from the launchers as they were before the plans
+moved into the header; they do not come from the code under test.
+
+Regenerate the table only when a launch is meant to change:  python3 tests/test_launch_plans.py --write
+(--include DIR builds the driver against the vhp_launch_plan.hpp in DIR instead of the package's)."""
+import itertools
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "visibility-heuristic-path-planner_amd", "csrc")
+DRIVER = os.path.join(HERE, "launch_plan_driver.cpp")
+TABLE = os.path.join(HERE, "golden", "launch_plans.json")
+SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+CUS = (256, 80, 304)
+# contexts, claim_ahead, heads, tail_pct, early_ctx, late_pct, busy_cap, static_round: as vhp_set_option leaves them
+POOL_AUTO = (0, -1, 0, 0, 0, 0, 0, 2)
+POOL_FIELDS = ("ok", "n_ctx", "waves", "lds_bytes", "n_head", "tail_limit", "early_ctx", "late_after", "claim_ahead", "busy_cap", "static_round",
+               "static_snake", "queue0")
+LAT_FIELDS = ("ok", "odd", "halves", "lds_bytes", "use_order_kernel")
+# {(contexts asked for, any-width build): the largest side at which that many fit the LDS}
+LDS_EDGES = {(16, 0): 6528, (16, 1): 6784, (3, 0): 36736, (3, 1): 38272, (2, 0): 55424, (2, 1): 57728, (1, 0): 111488, (1, 1): 116096}
+POOL_SIDES = [1000, 1023, 1024, 1025, 1026, 1663, 1664, 1665, 1666, 4096, 8192]
+
+
+def opts(**kw):
+    o = dict(zip(("contexts", "claim_ahead", "heads", "tail_pct", "early_ctx", "late_pct", "busy_cap", "static_round"), POOL_AUTO))
+    o.update(kw)
+    return tuple(o.values())
+
+
+# every key at its lowest and highest accepted value (vhp_set_option), and the values between that take another path
+POOL_OPTIONS = ([opts(contexts=v) for v in (1, 2, 3, 4, 16)] + [opts(claim_ahead=v) for v in (0, 64)] + [opts(heads=v) for v in (1, 3, 16)]
+                + [opts(tail_pct=v) for v in (1, 100)] + [opts(early_ctx=v) for v in (1, 2, 3, 16)] + [opts(late_pct=v) for v in (1, 100)]
+                + [opts(busy_cap=v) for v in (1, 16)] + [opts(static_round=v) for v in (0, 1)]
+                + [opts(contexts=4, early_ctx=3, late_pct=30), opts(contexts=16, heads=16, static_round=1)])
+
+
+def static_edges(n_cus, contexts=(1, 2, 3)):
+    """batch sizes at which contexts x n_cus units are reached, and one either side"""
+    return sorted({1, 9, 1024} | {-(-c * n_cus // 8) + d for c in contexts for d in (-1, 0, 1)})
+
+
+def widths(side):
+    """(nx, ny, any-width build): square, wide, a width that is no multiple of 8, and the any-width build on one that is (a field that
+    does not start on a 64-byte line)"""
+    return [(side, side, 0), (side, max(1, side // 3), 0), (side - side % 8 - 1, side, 1), (side - side % 8, side, 1)]
+
+
+def lat_flags(*names):
+    return tuple(int(n in names) for n in ("d_lat_order", "pivot_rec", "src_index", "slot_base", "map_idx", "planner_dev"))
+
+
+LAT_SIDES = [1024, 1025, 2048, 2049, 4096, 4097, 8192]
+LAT_SOURCES = list(range(1, 65)) + [255, 256, 257]
+LAT_FLAGS = ([lat_flags()] + [lat_flags(n) for n in ("pivot_rec", "src_index", "slot_base", "map_idx", "planner_dev")]
+             + [lat_flags("d_lat_order", n) for n in ("pivot_rec", "src_index", "slot_base", "map_idx", "planner_dev")])
+
+
+def grid():
+    """[(key, request without the batch size, batch sizes)]: each group answered for every batch size in its list."""
+    g = []
+    for side in POOL_SIDES:
+        for nx, ny, anyw in widths(side):
+            for n_cus in CUS:
+                g.append(("pool A", nx, ny, n_cus, anyw, POOL_AUTO, static_edges(n_cus)))
+    for (c, anyw), side in sorted(LDS_EDGES.items()):
+        for s in (side, side + 1):
+            g.append(("pool L", s - anyw, s, 256, anyw, opts(contexts=c), [1, 32 * c - 1, 32 * c]))
+    for side in (1000, 1025, 1665):
+        for nx, ny, anyw in ((side, side, 0), (side - side % 8 - 1, side, 1)):
+            for o in POOL_OPTIONS:
+                g.append(("pool O", nx, ny, 256, anyw, o, static_edges(256, (1, 2, 3, 4, 16))))
+    for side in LAT_SIDES:
+        for n_cus, asked in itertools.product(CUS, (0, 1, 2, 4, 8)):
+            g.append(("lat A", side, side, n_cus, 0, (asked,) + lat_flags("d_lat_order"), LAT_SOURCES))
+    for side in (1000, 1025):
+        for n_cus, f in itertools.product(CUS, LAT_FLAGS):
+            g.append(("lat F", side, side - 3, n_cus, 0, (0,) + f, [1, n_cus // 8, n_cus // 8 + 1, 256, 257]))
+    for nx, ny in ((1001, 1000), (2047, 2049)):
+        g.append(("lat O", nx, ny, 256, 1, (0,) + lat_flags("d_lat_order"), [1, 16, 32, 33, 256, 257]))
+    return g
+
+
+def key(row):
+    part, nx, ny, n_cus, build, o, _ = row
+    return "%s %dx%d cus%d %s%d opt%s" % (part, nx, ny, n_cus, "anyw" if part.startswith("pool") else "odd", build, ",".join(map(str, o)))
+
+
+def request(row, n_src):
+    part, nx, ny, n_cus, build, o, _ = row
+    return " ".join(map(str, (part.split()[0], nx, ny, n_src, n_cus, build) + tuple(o)))
+
+
+def pool_request(nx, ny, n_src, n_cus=256, anyw=0, **kw):
+    return request(("pool", nx, ny, n_cus, anyw, opts(**kw), None), n_src)
+
+
+def lat_request(nx, ny, n_src, n_cus=256, odd=0, asked=0, flags=("d_lat_order",)):
+    return request(("lat", nx, ny, n_cus, odd, (asked,) + lat_flags(*flags), None), n_src)
+
+
+def build_driver(out_dir, include=CSRC, sanitized=False):
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler (set CXX)"
+    exe = os.path.join(out_dir, "launch_plan_driver" + ("_san" if sanitized else ""))
+    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-DVHP_SIM"] + (SANITIZE if sanitized else ["-O1"])
+                          + ["-I", include, "-I", CSRC, "-o", exe, DRIVER])
+    return exe
+
+
+def ask(exe, requests):
+    """The driver's word for each request line."""
+    p = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, check=False)
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    out = p.stdout.split()
+    assert len(out) == len(requests)
+    return out
+
+
+def plans(exe, requests):
+    """... as dicts of the plan's members; queue0 as the launcher passes it on."""
+    res = []
+    for req, word in zip(requests, ask(exe, requests)):
+        v = word.split(",")
+        if req.startswith("pool"):
+            head, tail = v.pop().split("+")
+            v.append(int(head) | int(tail) << 32)
+        res.append(dict(zip(POOL_FIELDS if req.startswith("pool") else LAT_FIELDS, map(int, v))))
+    return res
+
+
+def all_requests():
+    return [request(row, n) for row in grid() for n in row[-1]]
+
+
+def dump(exe):
+    """{key: "plan plan*n ..."}: the driver's word per batch size of the group, runs of one plan as plan*length."""
+    out = ask(exe, all_requests())
+    table, i = {}, 0
+    for row in grid():
+        runs = [(p, len(list(r))) for p, r in itertools.groupby(out[i:i + len(row[-1])])]
+        table[key(row)] = " ".join(p if n == 1 else "%s*%d" % (p, n) for p, n in runs)
+        i += len(row[-1])
+    return table
+
+
+def lds_edges(exe):
+    """LDS_EDGES, by bisection: the LDS a number of contexts needs grows with the side, and a plan keeps the contexts that fit."""
+    edges = {}
+    for c, anyw in sorted(LDS_EDGES):
+        def keeps(side):
+            p = plans(exe, [pool_request(side - anyw, side, 8, anyw=anyw, contexts=c)])[0]
+            return p["ok"] and p["n_ctx"] == c
+        lo, hi = 1, 1 << 20
+        assert keeps(lo) and not keeps(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if keeps(mid) else (lo, mid)
+        edges[(c, anyw)] = lo
+    return edges
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return build_driver(str(tmp_path_factory.mktemp("launch_plans")))
+
+
+@pytest.fixture(scope="module")
+def table(exe):
+    return dump(exe)
+
+
+def test_launch_plans_match_table(table):
+    with open(TABLE) as f:
+        want = json.load(f)
+    assert want["fields"] == {"pool": list(POOL_FIELDS), "lat": list(LAT_FIELDS)}
+    assert want["sources"] == {key(row): row[-1] for row in grid()}, "the grid and the table's groups differ"
+    diff = [(k, want["plans"][k], table[k]) for k in sorted(table) if table[k] != want["plans"][k]]
+    assert not diff, "the launch plans moved away from the table at %d groups, e.g. %s" % (len(diff), diff[:3])
+
+
+def test_launch_plan_table_is_not_vacuous(table):
+    words = [(k.split()[0], p.split("*")[0].split(",")) for k, v in table.items() for p in v.split()]
+    pool = [dict(zip(POOL_FIELDS, w)) for kind, w in words if kind == "pool"]
+    lat = [dict(zip(LAT_FIELDS, w)) for kind, w in words if kind == "lat"]
+    assert {"1", "2", "3"} <= {p["n_ctx"] for p in pool if p["ok"] == "1"}
+    assert {p["static_round"] for p in pool} == {"0", "1"} and {p["static_snake"] for p in pool} == {"0", "1"}
+    assert {p["ok"] for p in pool} == {"0", "1"} and {p["waves"] for p in pool} == {"9", "12"}
+    assert {p["halves"] for p in lat} == {"1", "2", "4", "8"}
+    assert {p["use_order_kernel"] for p in lat} == {"0", "1"}
+
+
+# Derived by hand from launch_pool_t / pool_shape and launch_lat_t / lat_halves as they stood in vhp_pool.hip and vhp_lat.hip; fp64 fields,
+# 256 CUs, options as vhp_set_option leaves them unless said.
+Q_2_1 = 512 | 256 << 32   # two head contexts, one filler, 256 workgroups
+EXPECT_POOL = [
+    (dict(nx=1000, ny=1000, n_src=256), dict(n_ctx=3, waves=12, n_head=2, tail_limit=307, early_ctx=3, late_after=1024, claim_ahead=48, busy_cap=12,
+                                              static_round=1, static_snake=1, queue0=Q_2_1)),
+    (dict(nx=1001, ny=1000, n_src=256, anyw=1), dict(n_ctx=3, waves=9, n_head=2, tail_limit=307, early_ctx=3, late_after=1024, claim_ahead=48,
+                                                      busy_cap=9, static_round=1, static_snake=1, queue0=Q_2_1)),
+    (dict(nx=1025, ny=1025, n_src=256), dict(n_ctx=2, n_head=1)),
+    (dict(nx=1665, ny=1665, n_src=256), dict(n_ctx=1)),
+    (dict(nx=4096, ny=4096, n_src=128), dict(n_ctx=1, n_head=1, tail_limit=153, late_after=512, static_round=1, queue0=256)),
+    (dict(nx=136, ny=136, n_src=95), dict(static_round=0, queue0=0)),
+    (dict(nx=136, ny=136, n_src=96), dict(static_round=1, queue0=Q_2_1)),
+    (dict(nx=1000, ny=1000, n_src=256, contexts=4), dict(n_ctx=4, n_head=2, queue0=512 | 512 << 32)),
+    (dict(nx=1000, ny=1000, n_src=256, early_ctx=2), dict(static_round=0)),
+    (dict(nx=1000, ny=1000, n_src=256, static_round=1), dict(static_round=1, static_snake=0)),
+]
+EXPECT_LAT = [
+    (dict(nx=1000, ny=1000, n_src=1), dict(halves=1)),
+    (dict(nx=1000, ny=1000, n_src=1, asked=4), dict(halves=4)),
+    (dict(nx=2048, ny=2048, n_src=1), dict(halves=2)),
+    (dict(nx=2048, ny=2048, n_src=32), dict(halves=1)),
+    (dict(nx=4096, ny=4096, n_src=16), dict(halves=4)),
+    (dict(nx=8192, ny=8192, n_src=1), dict(halves=8)),
+    (dict(nx=8192, ny=8192, n_src=8), dict(halves=8)),
+    (dict(nx=1000, ny=1000, n_src=32), dict(use_order_kernel=0)),
+    (dict(nx=1000, ny=1000, n_src=33), dict(use_order_kernel=1)),
+    (dict(nx=1000, ny=1000, n_src=33, flags=("d_lat_order", "slot_base")), dict(use_order_kernel=0)),
+]
+
+
+def test_plans_derived_by_hand(exe):
+    asked = [pool_request(**kw) for kw, _ in EXPECT_POOL] + [lat_request(**kw) for kw, _ in EXPECT_LAT]
+    for (kw, want), got in zip(EXPECT_POOL + EXPECT_LAT, plans(exe, asked)):
+        assert got["ok"] == 1, kw
+        assert {k: got[k] for k in want} == want, kw
+
+
+def test_the_launch_ends_shapes_take_the_paths_their_comments_claim(exe):
+    """tests/pool_launch_ends_shapes.py at 256 CUs: three contexts everywhere, the static round where the comment says so"""
+    import pool_launch_ends_shapes as shapes
+    static = {"96_static_round": 1, "96_anyw": 1, "95_all_pulled": 0, "9_fewer_units_than_groups": 0}
+    names = sorted(shapes.SHAPES)
+    got = plans(exe, [pool_request(shapes.SHAPES[n][1], shapes.SHAPES[n][2], shapes.SHAPES[n][0], anyw=int(shapes.SHAPES[n][1] % 8 != 0)) for n in names])
+    for n, p in zip(names, got):
+        assert p["ok"] == 1 and p["n_ctx"] == 3, n
+        if n in static:
+            assert p["static_round"] == static[n], n
+    assert set(static) <= set(names)
+
+
+def test_the_lds_edges_are_where_the_grid_says(exe):
+    assert lds_edges(exe) == LDS_EDGES
+
+
+def test_the_grids_the_library_takes(exe):
+    """pool_supported / lat_supported: every side up to VHP_MAX_SIDE, nothing beyond, nothing empty"""
+    asked = [(1, 1), (8192, 8192), (8192, 1), (1, 8192), (8193, 8), (8, 8193), (0, 8), (8, 0), (-1, 8)]
+    assert ask(exe, ["grid %d %d" % g for g in asked]) == ["1,1"] * 4 + ["0,0"] * 5
+
+
+def test_driver_under_the_sanitizers_agrees(exe, tmp_path):
+    assert ask(build_driver(str(tmp_path), sanitized=True), all_requests()) == ask(exe, all_requests())
+
+
+if __name__ == "__main__":
+    import argparse
+    import tempfile
+    ap = argparse.ArgumentParser(description="write tests/golden/launch_plans.json from plan_pool and plan_lat")
+    ap.add_argument("--write", action="store_true")
+    ap.add_argument("--edges", action="store_true", help="print LDS_EDGES as the driver finds them")
+    ap.add_argument("--include", default=CSRC, help="directory of the vhp_launch_plan.hpp to build against")
+    args = ap.parse_args()
+    with tempfile.TemporaryDirectory() as d:
+        drv = build_driver(d, args.include)
+        if args.edges:
+            print(lds_edges(drv))
+        t = dump(drv) if args.write else None
+    if t:
+        with open(TABLE, "w") as f:
+            json.dump({"fields": {"pool": POOL_FIELDS, "lat": LAT_FIELDS}, "sources": {key(row): row[-1] for row in grid()}, "plans": t}, f,
+                      indent=0, sort_keys=True)
+            f.write("\n")
+        print("wrote %d groups to %s" % (len(t), TABLE), file=sys.stderr)

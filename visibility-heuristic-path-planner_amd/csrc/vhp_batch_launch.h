@@ -6,6 +6,8 @@
 
 #include <functional>
 
+#include "vhp_launch_plan.hpp"
+
 namespace vhp {
 
 struct PlannerDev;  // (vhp_planner_dev.hip.h)
@@ -57,13 +59,7 @@ struct BatchArgs {
   std::function<hipError_t(const void*, size_t)> raise_lds;
   // optional per-launch timing events, recorded around the sweep kernel only
   hipEvent_t ev_begin, ev_end;
-  int pool_contexts = 0;  // pool sweep: units a workgroup holds at once (0: automatic; vhp_set_option "pool_contexts")
-  int pool_claim_ahead = -1;  // pool sweep: steps by which a strip is claimed ahead of the strip below's progress (-1: automatic)
-  int pool_heads = 0;     // pool sweep: contexts that pull from the head of the size-sorted queue (0: one)
-  int pool_tail_pct = 0;  // pool sweep: share of the units (by count, smallest first) that the filler contexts may take from the small end (0: 50)
-  int pool_early_ctx = 0, pool_late_pct = 0;  // pool sweep: contexts >= early_ctx open once late_pct % of the units are taken (0: all open)
-  int pool_busy_cap = 0;  // pool sweep: a workgroup takes another unit only while fewer wavefronts than this are sweeping (0: no cap)
-  int pool_static_round = 2;  // pool sweep: every context's first unit by workgroup index, no pull (vhp_pool.hpp Args::static_round; 2: odd head contexts count down, Args::static_snake); 0: every unit pulled
+  PoolOpts pool;          // pool sweep: the vhp_set_option keys of its launch plan (vhp_launch_plan.hpp plan_pool)
   LatLaunch lat;          // latency sweep: the launch of a planner's loop
   unsigned long long pool_epoch = 0;  // pool sweep: the tag of this launch's boundary-line entries: never 0, never reused on this scratch
   int n_maps = 0;         // maps behind rows / cols / dmap (PackedMaps::n)
@@ -74,10 +70,12 @@ inline void set_maps(BatchArgs& a, const PackedMaps& m) {
   a.wpr = m.wpr; a.wpc = m.wpc; a.nx = m.nx; a.ny = m.ny;
   a.n_maps = m.n;
 }
+// ... and as the two kernels take them (map 0 of a stack)
+inline geom::Map geom_map(const BatchArgs& a) { return {a.rows, a.cols, a.recip, a.wpr, a.wpc, a.nx, a.ny}; }
 
 // The pool sweep (vhp_pool.hip): d_queue is scratch of pool_scratch_bytes (pull counter, unit order, the
 // diagonal lines of the y-major units, the boundary lines of the strips) that is ZERO when it is first used and is
-// written by nothing else; pool_epoch differs from launch to launch.
+// written by nothing else; pool_epoch differs from launch to launch.  (pool_supported, lat_supported: defined in vhp_launch_plan.hpp)
 bool pool_supported(int nx, int ny);
 hipError_t launch_pool(const BatchArgs& a);
 size_t pool_scratch_bytes(int n_src, int nx, int ny);

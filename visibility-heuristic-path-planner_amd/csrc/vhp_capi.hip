@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -71,17 +72,11 @@ struct vhp_ctx {
   int opt_multi = 0;          // 1: force the multi-round build
   int opt_slide = -1;         // 0 / 1: y-major column grid slid onto 128-byte lines
   int opt_pack = 0;           // 1: pack short quadrants into one workgroup
-  int opt_lat_workgroups = 0; // latency sweep: workgroups per octant (0 automatic, 1 / 2 / 4 / 8: vhp_lat.hip lat_halves)
+  int opt_lat_workgroups = 0; // latency sweep: workgroups per octant (0 automatic, 1 / 2 / 4 / 8: vhp_launch_plan.hpp lat_halves)
   int opt_kernel = 0;         // 0 auto, 1 front sweep (vhp_sweep_fronts), 3 pool sweep (vhp_pool), 4 latency sweep (vhp_lat); 2 was the streaming sweep (retired in round 4)
   int last_kernel = 0;         // what the last batch sweep launched: 1 front sweep, 3 pool sweep, 4 latency sweep
   long long opt_field_stride = 0;  // device-pointer batch sweeps: elements from one field to the next (0: nx * ny, packed)
-  int opt_pool_claim_ahead = -1;  // pool sweep: claim a strip this many steps ahead (-1 auto)
-  int opt_pool_contexts = 0;   // pool sweep: units a workgroup holds at once (0 auto)
-  int opt_pool_heads = 0;      // pool sweep: contexts that pull the largest units (0 auto)
-  int opt_pool_tail_pct = 0;   // pool sweep: share of the units the filler contexts take from the small end (0 auto)
-  int opt_pool_early_ctx = 0, opt_pool_late_pct = 0;  // pool sweep: late contexts (0 auto)
-  int opt_pool_busy_cap = 0;   // pool sweep: no new unit while this many wavefronts of the workgroup are sweeping (0 auto)
-  int opt_pool_static_round = 2;  // pool sweep: every context's first unit by workgroup index (2: the second head context counts down; 0: every unit pulled from the queue)
+  vhp::PoolOpts opt_pool;   // pool sweep: the "pool_*" keys (vhp_launch_plan.hpp plan_pool)
 
   vhp::PlannerState pl;  // device-resident planner state
   vhp::SpecState spec;   // field cache of the speculative planner
@@ -346,14 +341,7 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const vhp::PackedMaps& m, const int32_
   a.n_cus = c->n_cus;
   a.stream = c->stream;
   a.raise_lds = [c](const void* fn, size_t bytes) { return raise_lds_limit(c, fn, bytes); };
-  a.pool_contexts = c->opt_pool_contexts;
-  a.pool_claim_ahead = c->opt_pool_claim_ahead;
-  a.pool_busy_cap = c->opt_pool_busy_cap;
-  a.pool_early_ctx = c->opt_pool_early_ctx;
-  a.pool_late_pct = c->opt_pool_late_pct;
-  a.pool_tail_pct = c->opt_pool_tail_pct;
-  a.pool_heads = c->opt_pool_heads;
-  a.pool_static_round = c->opt_pool_static_round;
+  a.pool = c->opt_pool;
   EventPair ev;
   if (hipError_t ee = acquire_events(c, o.timed, &ev); ee != hipSuccess) return ee;
   a.ev_begin = ev.first;
@@ -1065,30 +1053,51 @@ int vhp_timing(vhp_ctx* ctx, int enable) {
   return VHP_OK;
 }
 
+namespace {
+// vhp_set_option's int keys: the values a key takes (min .. max, and `ok` where the domain is no interval), what a refusal says and
+// where the value goes.  flag: any value, kept as 0 / 1.
+struct OptionKey {
+  const char* key;
+  int min, max;
+  const char* message;
+  int& (*at)(vhp_ctx*);
+  bool (*ok)(int) = nullptr;
+  bool flag = false;
+};
+const OptionKey kOptionKeys[] = {
+    {"rows_per_lane", 0, 4, "rows_per_lane: 0, 1, 2 or 4", [](vhp_ctx* c) -> int& { return c->opt_rows_per_lane; }, [](int v) { return v != 3; }},
+    {"strips", 0, 8, "strips: 0..8", [](vhp_ctx* c) -> int& { return c->opt_strips; }},
+    {"multi_round", INT_MIN, INT_MAX, "", [](vhp_ctx* c) -> int& { return c->opt_multi; }, nullptr, true},
+    {"slide", -1, 1, "slide: -1, 0 or 1", [](vhp_ctx* c) -> int& { return c->opt_slide; }},
+    {"pack", INT_MIN, INT_MAX, "", [](vhp_ctx* c) -> int& { return c->opt_pack; }, nullptr, true},
+    {"lat_workgroups", 0, 8, "lat_workgroups: 0 (automatic), 1, 2, 4 or 8", [](vhp_ctx* c) -> int& { return c->opt_lat_workgroups; }, [](int v) { return v <= 2 || v == 4 || v == 8; }},
+    {"kernel", 0, 4, "kernel: 0 auto, 1 fronts, 3 pool, 4 latency (2, the streaming sweep, was retired)", [](vhp_ctx* c) -> int& { return c->opt_kernel; }, [](int v) { return v != 2; }},
+    {"pool_claim_ahead", -1, 64, "pool_claim_ahead: -1 (automatic) .. 64", [](vhp_ctx* c) -> int& { return c->opt_pool.claim_ahead; }},
+    {"pool_heads", 0, 16, "pool_heads: 0 (automatic) .. 16", [](vhp_ctx* c) -> int& { return c->opt_pool.heads; }},
+    {"pool_tail_pct", 0, 100, "pool_tail_pct: 0 (automatic) .. 100", [](vhp_ctx* c) -> int& { return c->opt_pool.tail_pct; }},
+    {"pool_early_ctx", 0, 16, "pool_early_ctx: 0 (automatic) .. 16", [](vhp_ctx* c) -> int& { return c->opt_pool.early_ctx; }},
+    {"pool_late_pct", 0, 100, "pool_late_pct: 0 (automatic) .. 100", [](vhp_ctx* c) -> int& { return c->opt_pool.late_pct; }},
+    {"pool_busy_cap", 0, 16, "pool_busy_cap: 0 (automatic) .. 16", [](vhp_ctx* c) -> int& { return c->opt_pool.busy_cap; }},
+    {"pool_contexts", 0, 16, "pool_contexts: 0 (automatic) .. 16", [](vhp_ctx* c) -> int& { return c->opt_pool.contexts; }},
+    {"pool_static_round", 0, 2, "pool_static_round: 0, 1 or 2", [](vhp_ctx* c) -> int& { return c->opt_pool.static_round; }},
+    {"planner_batch_group", 0, vhp::kBatchMaxGroup, "planner_batch_group: 0 (automatic) .. 32", [](vhp_ctx* c) -> int& { return c->opt_planner_batch_group; }},
+    {"alloc_budget_pct", 1, 90, "alloc_budget_pct: 1 .. 90 (per cent of the free device memory)", [](vhp_ctx* c) -> int& { return c->opt_alloc_budget_pct; }},
+};
+}  // namespace
+
 int vhp_set_option(vhp_ctx* ctx, const char* key, long long value) {
   if (!ctx || !key) return VHP_ERR_ARG;
   const std::string k(key);
   const int v = (int)value;
-  if (k == "rows_per_lane") { if (v != 0 && v != 1 && v != 2 && v != 4) return fail(ctx, VHP_ERR_ARG, "rows_per_lane: 0, 1, 2 or 4"); ctx->opt_rows_per_lane = v; }
-  else if (k == "strips") { if (v < 0 || v > 8) return fail(ctx, VHP_ERR_ARG, "strips: 0..8"); ctx->opt_strips = v; }
-  else if (k == "multi_round") { ctx->opt_multi = v != 0; }
-  else if (k == "slide") { if (v < -1 || v > 1) return fail(ctx, VHP_ERR_ARG, "slide: -1, 0 or 1"); ctx->opt_slide = v; }
-  else if (k == "pack") { ctx->opt_pack = v != 0; }
-  else if (k == "lat_workgroups") { if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return fail(ctx, VHP_ERR_ARG, "lat_workgroups: 0 (automatic), 1, 2, 4 or 8"); ctx->opt_lat_workgroups = v; }
-  else if (k == "kernel") { if (v < 0 || v > 4 || v == 2) return fail(ctx, VHP_ERR_ARG, "kernel: 0 auto, 1 fronts, 3 pool, 4 latency (2, the streaming sweep, was retired)"); ctx->opt_kernel = v; }
-  else if (k == "field_stride") { if (value < 0) return fail(ctx, VHP_ERR_ARG, "field_stride: 0 (packed) or elements per field"); ctx->opt_field_stride = value; }
-  else if (k == "pool_claim_ahead") { if (v < -1 || v > 64) return fail(ctx, VHP_ERR_ARG, "pool_claim_ahead: -1 (automatic) .. 64"); ctx->opt_pool_claim_ahead = v; }
-  else if (k == "pool_heads") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_heads: 0 (automatic) .. 16"); ctx->opt_pool_heads = v; }
-  else if (k == "pool_tail_pct") { if (v < 0 || v > 100) return fail(ctx, VHP_ERR_ARG, "pool_tail_pct: 0 (automatic) .. 100"); ctx->opt_pool_tail_pct = v; }
-  else if (k == "pool_early_ctx") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_early_ctx: 0 (automatic) .. 16"); ctx->opt_pool_early_ctx = v; }
-  else if (k == "pool_late_pct") { if (v < 0 || v > 100) return fail(ctx, VHP_ERR_ARG, "pool_late_pct: 0 (automatic) .. 100"); ctx->opt_pool_late_pct = v; }
-  else if (k == "pool_busy_cap") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_busy_cap: 0 (automatic) .. 16"); ctx->opt_pool_busy_cap = v; }
-  else if (k == "pool_contexts") { if (v < 0 || v > 16) return fail(ctx, VHP_ERR_ARG, "pool_contexts: 0 (automatic) .. 16"); ctx->opt_pool_contexts = v; }
-  else if (k == "pool_static_round") { if (v < 0 || v > 2) return fail(ctx, VHP_ERR_ARG, "pool_static_round: 0, 1 or 2"); ctx->opt_pool_static_round = v; }
-  else if (k == "planner_batch_group") { if (v < 0 || v > vhp::kBatchMaxGroup) return fail(ctx, VHP_ERR_ARG, "planner_batch_group: 0 (automatic) .. 32"); ctx->opt_planner_batch_group = v; }
-  else if (k == "alloc_budget_pct") { if (v < 1 || v > 90) return fail(ctx, VHP_ERR_ARG, "alloc_budget_pct: 1 .. 90 (per cent of the free device memory)"); ctx->opt_alloc_budget_pct = v; }
-  else return fail(ctx, VHP_ERR_ARG, "vhp_set_option: unknown key '" + k + "'");
-  return VHP_OK;
+  // (the one key that takes all 64 bits of its value)
+  if (k == "field_stride") { if (value < 0) return fail(ctx, VHP_ERR_ARG, "field_stride: 0 (packed) or elements per field"); ctx->opt_field_stride = value; return VHP_OK; }
+  for (const OptionKey& o : kOptionKeys) {
+    if (k != o.key) continue;
+    if (v < o.min || v > o.max || (o.ok && !o.ok(v))) return fail(ctx, VHP_ERR_ARG, o.message);
+    o.at(ctx) = o.flag ? v != 0 : v;
+    return VHP_OK;
+  }
+  return fail(ctx, VHP_ERR_ARG, "vhp_set_option: unknown key '" + k + "'");
 }
 
 int vhp_last_sweep_kernel(const vhp_ctx* ctx) { return ctx ? ctx->last_kernel : 0; }

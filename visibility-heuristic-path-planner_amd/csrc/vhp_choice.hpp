@@ -23,7 +23,7 @@ struct ChoiceIn {
   int nx = 0, ny = 0, n_src = 0, n_cus = 256;
   bool f64 = true;
   ChoiceOpts opt;
-  // evaluated by the caller on device-side constants: lat_supported, pool_supported, lat_scratch_bytes(n_src) <= 2 GiB
+  // evaluated by the caller: lat_supported, pool_supported (vhp_launch_plan.hpp), lat_scratch_bytes(n_src) <= 2 GiB (vhp_lat.hip)
   bool lat_ok = false, pool_ok = false, lat_scratch_fits = false;
 };
 

@@ -15,28 +15,17 @@
 namespace vhp {
 namespace pool {
 
-// One workgroup per unit (octant of a quadrant of a source); strip p is wavefront p mod kLatWaves's.  Eight wavefronts: two per
-// SIMD, 256 vector registers each (a window keeps its 17 + 16 operands and the 16 pairs of its tile read-out in registers).
-#ifndef VHP_LAT_WAVES
-#define VHP_LAT_WAVES 8
-#endif
-constexpr int kLatWaves = VHP_LAT_WAVES;
+// One workgroup per unit (octant of a quadrant of a source) of kLatWaves strip wavefronts (vhp_launch_plan.hpp, with LatWorkerT).
 
 #ifdef VHP_DIAG_POOLPROF  // diagnostic builds only (tools/lat_timeline.py)
 __device__ unsigned long long g_latprof[256 * 16 * 20];
 __device__ unsigned long long g_lat_strip_times[64 * 48 * 4];
 #endif
 
-#ifdef VHP_LAT_STRIPS  // A/B builds only: the sweep in strips of rows (vhp_lat.hpp), what the kernel was until round 6
-template <typename OutT, bool ODD, bool MULTI = false> using LatWorkerT = LatWorker<OutT, ODD>;
-#else
-template <typename OutT, bool ODD, bool MULTI = false> using LatWorkerT = BandWorker<OutT, ODD, MULTI>;
-#endif
 // wavefronts of a workgroup: kLatWaves sweepers and, in the band sweep, a storer beside each (16: four per SIMD, 128 vector registers)
 constexpr int kLatThreads = 64 * kLatWaves * LatWorkerT<double, false>::kRoles;
-constexpr int kLatTilePitch = LatWorkerT<double, false>::kTilePitch;
 
-// MULTI: the build for launches with more than one workgroup per unit (lat_halves below): its bands can read across workgroups
+// MULTI: the build for launches with more than one workgroup per unit (vhp_launch_plan.hpp lat_halves): its bands can read across workgroups
 template <typename OutT, bool ODD, bool MULTI>
 __global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_sweep(LatArgs<OutT> a) {
   extern __shared__ double lds[];
@@ -144,7 +133,6 @@ __global__ void vhp_pack_diag_stack(const uint64_t* __restrict__ rows, uint64_t*
 // The units of a launch (8 per source: quadrant x {x-major, y-major}) by falling length of their march, for launches of more workgroups
 // than the chip holds at once: a counting sort by steps / 8 in one workgroup (up to 1024 x kLatOrderPerThread units).  The length of a march is what an
 // octant's time goes by (T / 16 + T / 64 windows); units of sources outside the grid go last.
-constexpr int kLatOrderPerThread = 2;   // (256 sources)
 __global__ void __launch_bounds__(1024) vhp_lat_order(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order) {
   __shared__ int hist[1024], start[1024];
   const int tid = (int)threadIdx.x, n_units = n_src * kUnits;
@@ -189,53 +177,27 @@ __global__ void __launch_bounds__(1024) vhp_lat_order(const int32_t* __restrict_
 }  // namespace pool
 
 namespace {
-constexpr size_t kLdsLimit = 160 * 1024;
-#ifndef VHP_LAT_HALVES_MIN_SIDE
-#define VHP_LAT_HALVES_MIN_SIDE 1024
-#endif
-// Workgroups per unit of a latency-sweep launch (LatArgs::halves; vhp_band.hpp BandWorker).  One up to 1024 cells a side: an octant
-// has at most 16 bands there, and what bands 8-15 gain by not waiting for the sweepers of bands 0-7 the hand-over through global
-// memory takes back (measured at 1000^2: 117.8 / 118.4 us over eight source positions).  Above: two up to 2048, four up to 4096, eight
-// beyond -- an octant of P bands is swept in rounds of 8 x that number, and every round waits for the one before (8192^2, one source:
-// 3.47 ms with one workgroup per unit, 1.92 with two, 1.18 with four), halved until the launch is at most twice the chip.  (asked: vhp_set_option "lat_workgroups", 1 / 2 / 4 / 8, for
-// measurements and tests; 0: by the size.)
-int lat_halves(int n_src, int nx, int ny, int n_cus, int asked) {
-  const int cus = n_cus > 0 ? n_cus : 256, side = std::max(nx, ny);
-  const int want = asked > 0 ? asked : side > 4 * VHP_LAT_HALVES_MIN_SIDE ? 8 : side > 2 * VHP_LAT_HALVES_MIN_SIDE ? 4 : side > VHP_LAT_HALVES_MIN_SIDE ? 2 : 1;
-  int h = 1;
-  // (up to twice as many workgroups as CUs -- a launch of more workgroups than CUs is safe, BandWorker::run, and a unit's later
-  // workgroups start while its first ones are at their first bands: 16 sources at 4096^2 1265 us with two workgroups per unit, 1193 with
-  // four; 8 at 8192^2 2718 with four, 2447 with eight; a number that was asked for is taken as it is)
-  // (... beyond two that fit: 32 sources at 1536^2 take 280 us with one workgroup per unit and 316 with two on twice the chip)
-  while (2 * h <= want && 2 * h <= 8 && (asked > 0 || 2 * h * pool::kUnits * n_src <= (h >= 2 ? 2 : 1) * cus)) h *= 2;
-  return h;
-}
-size_t lat_lds_bytes(int nx, int ny) { return (size_t)pool::make_layout(pool::kLatWaves, 1, nx, ny, pool::kLatTilePitch).total * 8; }
-
+// (workgroups per unit, the LDS and whether the units are ordered first: vhp_launch_plan.hpp plan_lat)
 template <typename OutT>
 hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   using namespace pool;
-  const bool odd = lat_needs_odd<OutT>(a.nx, a.field_stride, static_cast<const OutT*>(a.d_out));
-  int halves = lat_halves(a.n_src, a.nx, a.ny, a.n_cus, a.lat_workgroups);
-#if defined(VHP_LAT_STRIPS)
-  halves = 1;
-#endif
+  const LatPlan p = plan_lat(a.nx, a.ny, a.n_src, a.n_cus, lat_needs_odd<OutT>(a.nx, a.field_stride, static_cast<const OutT*>(a.d_out)), a.lat_workgroups,
+                             {a.d_lat_order != nullptr, a.lat.pivot_rec != nullptr, a.lat.src_index != nullptr, a.lat.slot_base != nullptr,
+                              a.lat.map_idx != nullptr, pd != nullptr});
 #ifdef VHP_EXP_ONE_KERNEL  // compile-time experiments only: one instantiation instead of eight
   auto k = vhp_lat_sweep<double, false, false>;
-  halves = 1;
-  if (odd || sizeof(OutT) != 8) return hipErrorInvalidValue;
+  if (p.odd || sizeof(OutT) != 8) return hipErrorInvalidValue;
 #else
-  auto k = halves > 1 ? (odd ? vhp_lat_sweep<OutT, true, true> : vhp_lat_sweep<OutT, false, true>)
-                      : (odd ? vhp_lat_sweep<OutT, true, false> : vhp_lat_sweep<OutT, false, false>);
+  auto k = p.halves > 1 ? (p.odd ? vhp_lat_sweep<OutT, true, true> : vhp_lat_sweep<OutT, false, true>)
+                        : (p.odd ? vhp_lat_sweep<OutT, true, false> : vhp_lat_sweep<OutT, false, false>);
 #endif
   // a stack of maps (a.lat.map_idx): the fp64 build of the kernel that reads a map per source
-  auto ks = halves > 1 ? (odd ? vhp_lat_maps_sweep<true, true> : vhp_lat_maps_sweep<false, true>)
-                       : (odd ? vhp_lat_maps_sweep<true, false> : vhp_lat_maps_sweep<false, false>);
+  auto ks = p.halves > 1 ? (p.odd ? vhp_lat_maps_sweep<true, true> : vhp_lat_maps_sweep<false, true>)
+                         : (p.odd ? vhp_lat_maps_sweep<true, false> : vhp_lat_maps_sweep<false, false>);
   if (a.lat.map_idx && (sizeof(OutT) != 8 || pd)) return hipErrorInvalidValue;
-  const size_t lds = lat_lds_bytes(a.nx, a.ny);
-  if (lds > kLdsLimit || a.pool_epoch == 0) return hipErrorInvalidValue;
+  if (!p.ok || a.pool_epoch == 0) return hipErrorInvalidValue;
   if (a.raise_lds) {
-    hipError_t e = a.raise_lds(a.lat.map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), lds);
+    hipError_t e = a.raise_lds(a.lat.map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), p.lds_bytes);
     if (e != hipSuccess) return e;
   }
 #ifdef VHP_EXP_ONE_KERNEL
@@ -243,8 +205,7 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
 #else
   LatArgs<OutT> g;
 #endif
-  g.m.rows = a.rows; g.m.cols = a.cols; g.m.recip = a.recip;
-  g.m.wpr = a.wpr; g.m.wpc = a.wpc; g.m.nx = a.nx; g.m.ny = a.ny;
+  g.m = geom_map(a);
   g.src_xy = a.d_src;
 #ifdef VHP_EXP_ONE_KERNEL
   g.out = static_cast<double*>(a.d_out);
@@ -268,29 +229,28 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   // Two workgroups per unit where an octant can have more bands than a workgroup has sweepers and the launch leaves the CUs for it
   // (vhp_band.hpp BandWorker: bands 8-15, 24-31, ... of an octant on the second one).
   g.n_units = a.n_src * kUnits;
-  g.halves = halves;
+  g.halves = p.halves;
 #ifdef VHP_DIAG_POOLPROF
-  { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(pool::g_lat_strip_times)) == hipSuccess) g.strip_times = static_cast<unsigned long long*>(p); }
+  { void* sym = nullptr; if (hipGetSymbolAddress(&sym, HIP_SYMBOL(pool::g_lat_strip_times)) == hipSuccess) g.strip_times = static_cast<unsigned long long*>(sym); }
 #endif
   if (a.ev_begin) (void)hipEventRecord(a.ev_begin, a.stream);
 #ifndef VHP_EXP_ONE_KERNEL
   if constexpr (sizeof(OutT) == 8) {
     if (pd) {  // the planner's iteration: the sweep's eight workgroups and the epilogue's in one launch
-      auto kp = odd ? vhp_planner_iteration<true> : vhp_planner_iteration<false>;
+      auto kp = p.odd ? vhp_planner_iteration<true> : vhp_planner_iteration<false>;
       if (a.raise_lds) {
-        hipError_t e2 = a.raise_lds(reinterpret_cast<const void*>(kp), lds);
+        hipError_t e2 = a.raise_lds(reinterpret_cast<const void*>(kp), p.lds_bytes);
         if (e2 != hipSuccess) return e2;
       }
       g.halves = 1;
-      hipLaunchKernelGGL(kp, dim3((unsigned)(kUnits + kPlanEpiBlocks)), dim3(kLatThreads), lds, a.stream, g, *pd);
+      hipLaunchKernelGGL(kp, dim3((unsigned)(kUnits + kPlanEpiBlocks)), dim3(kLatThreads), p.lds_bytes, a.stream, g, *pd);
       const hipError_t e3 = hipGetLastError();
       if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);
       return e3;
     }
   }
 #endif
-  if (g.halves == 1 && a.n_src * kUnits > (a.n_cus > 0 ? a.n_cus : 256) && a.n_src * kUnits <= 1024 * pool::kLatOrderPerThread && a.d_lat_order && !a.lat.pivot_rec && !a.lat.src_index && !a.lat.slot_base) {
-    // more workgroups than the chip holds at once: the long units first
+  if (p.use_order_kernel) {
     // (a list of its own, not a corner of the scratch: nothing but tagged entries may ever be written where a later launch looks for tags)
     hipLaunchKernelGGL(pool::vhp_lat_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, a.d_lat_order);
     g.order = a.d_lat_order;
@@ -298,10 +258,10 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   if (a.lat.map_idx) {
     if constexpr (sizeof(OutT) == 8) {
       const LatMapStack st{a.lat.map_idx, a.n_maps, (long long)a.ny * a.wpr, (long long)a.nx * a.wpc, (long long)DiagMaps::words(a.nx, a.ny)};
-      hipLaunchKernelGGL(ks, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g, st);
+      hipLaunchKernelGGL(ks, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), p.lds_bytes, a.stream, g, st);
     }
   } else {
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), lds, a.stream, g);
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), p.lds_bytes, a.stream, g);
   }
   const hipError_t e = hipGetLastError();
   if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);
@@ -327,12 +287,6 @@ hipError_t lat_pack_diag_stack(const uint64_t* d_rows, int n_maps, int nx, int n
   const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernel steps through more maps than that)
   hipLaunchKernelGGL(pool::vhp_pack_diag_stack, dim3((unsigned)((words + 255) / 256), gy), dim3(256), 0, stream, d_rows, d_dmap, n_maps, nx, ny, wpr);
   return hipGetLastError();
-}
-
-bool lat_supported(int nx, int ny) {
-  if (nx <= 0 || ny <= 0 || nx > VHP_MAX_SIDE || ny > VHP_MAX_SIDE) return false;
-  // (a y-major workgroup keeps its quadrant's diagonal where an x-major one has its tiles)
-  return lat_lds_bytes(nx, ny) <= kLdsLimit && (size_t)pool::kLatWaves * pool::kXRows * pool::kTStride >= (size_t)(nx < ny ? nx : ny);
 }
 
 #ifdef VHP_DIAG_POOLPROF

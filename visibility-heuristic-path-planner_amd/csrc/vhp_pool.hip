@@ -10,19 +10,7 @@
 namespace vhp {
 namespace pool {
 
-// One persistent workgroup per CU; every wavefront is a Worker.  kWaves wavefronts: three per SIMD, 168 vector registers each
-// (the builds use 121 and 114).
-#ifndef VHP_POOL_WAVES
-#define VHP_POOL_WAVES 12
-#endif
-constexpr int kWaves = VHP_POOL_WAVES;
-// the build for widths that are not a multiple of 8: its tiles are three windows (12.8 KB a wavefront), nine wavefronts fit the LDS
-#ifndef VHP_POOL_WAVES_ANYW
-#define VHP_POOL_WAVES_ANYW 9
-#endif
-constexpr int kWavesAny = VHP_POOL_WAVES_ANYW;
-
-
+// One persistent workgroup per CU; every wavefront is a Worker (kWaves, kWavesAny: vhp_launch_plan.hpp).
 template <typename OutT, bool ANYW>
 __global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, int n_ctx) {
   extern __shared__ double lds[];
@@ -42,7 +30,6 @@ __global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, i
 // k-th unit in launch order.  Units of out-of-range sources weigh nothing, sort last and carry -1 in place of the source (they
 // are rejected when they are installed).  If the lines do not fit `capacity_blocks` (the launcher sizes the scratch by an upper
 // bound, so they do) nothing is swept and the error flag says so.
-constexpr int kBuckets = 1024;
 constexpr int kOrderLdsUnits = 8192;  // batches of up to 1024 sources are ordered in LDS alone (order_units_lds)
 
 // exclusive prefix sums over arr[0..n), in place, by the 1024 threads of the workgroup (a contiguous chunk each); returns the total
@@ -89,18 +76,7 @@ __device__ __forceinline__ void order_units(const int32_t* __restrict__ src_xy, 
       UnitGeo g;
       g.init(nx, ny, qo, sx, sy);
       nb = g.line_blocks();
-      double cells = 0.0;
-      if (g.n_strips > 0) {
-        if (g.x_major) { const double r = g.rows_total; cells = r * g.ni - r * (r - 1) * 0.5; }
-        else { const double c = g.cols_total; cells = c * (g.nj - 1) - c * (c - 1) * 0.5; }
-      }
-      // Launch order = how early a unit has to start, not how large it is: a unit is as long as its march (a thin octant along
-      // an axis is one strip, i.e. one wavefront, for 15 blocks: sorted by cells it started last and the launch ended on it),
-      // so the key is mostly the march length; among equally long ones the larger first.
-      const double march = (double)(g.x_major ? g.ni : g.nj) * inv_side;
-      double f = 0.8 * march + 0.2 * (cells * inv_area * 1.6 > 1.0 ? 1.0 : cells * inv_area * 1.6);
-      if (f > 1.0) f = 1.0;
-      bucket = (kBuckets - 1) - (int)(f * (kBuckets - 1));
+      bucket = unit_launch_bucket(g, inv_area, inv_side);
     }
     blocks[u] = nb | (bucket << 20);  // (nb < 2^20: a unit has at most 129 strips of 130 blocks)
     atomicAdd(&hist[bucket], 1);
@@ -154,16 +130,7 @@ __device__ __forceinline__ void order_units_lds(const int32_t* __restrict__ src_
       UnitGeo g;
       g.init(nx, ny, qo, sx, sy);
       nb = g.line_blocks();
-      double cells = 0.0;
-      if (g.n_strips > 0) {
-        if (g.x_major) { const double r = g.rows_total; cells = r * g.ni - r * (r - 1) * 0.5; }
-        else { const double c = g.cols_total; cells = c * (g.nj - 1) - c * (c - 1) * 0.5; }
-      }
-      // (the key of order_units, term for term)
-      const double march = (double)(g.x_major ? g.ni : g.nj) * inv_side;
-      double f = 0.8 * march + 0.2 * (cells * inv_area * 1.6 > 1.0 ? 1.0 : cells * inv_area * 1.6);
-      if (f > 1.0) f = 1.0;
-      bucket = (kBuckets - 1) - (int)(f * (kBuckets - 1));
+      bucket = unit_launch_bucket(g, inv_area, inv_side);
     }
     unit_key[u] = nb | (bucket << 20);
     if (qo == 0) src_key[s] = inside ? (sx | (sy << 16)) : -1;
@@ -222,45 +189,21 @@ __global__ void __launch_bounds__(1024) vhp_pool_order(const int32_t* __restrict
 }  // namespace pool
 
 namespace {
-constexpr size_t kLdsLimit = 160 * 1024;
-// (the sizes of a launch's scratch -- kQueueInts, head_bytes, diag_bytes, line_blocks_per_source: vhp_pool_scratch.hpp)
-
-struct PoolShape { int n_ctx; size_t lds; };
-// as many contexts (units a workgroup holds at once) as asked for (default 4) that fit the LDS
-// Measured (tools/ab_libs.py on one buffer, final launch order): 256 sources at 1000^2, 2 / 3 / 4 / 5 contexts 0.69 / 0.67-0.70 /
-// 0.74 / 0.77 ms; 128 sources at 2048^2, 1 / 2 / 3 contexts 1.25 / 1.38 / 1.41 ms; at 4096^2 1 / 2: 3.88 / 4.80 ms -- units that
-// large (a 4096^2 octant is 67 MB, 64 strips) keep every wavefront busy by themselves and only lose to a neighbour.
-PoolShape pool_shape(int nx, int ny, int force_ctx, bool anyw) {
-  PoolShape s;
-  // Round 4 (non-temporal stores, strips claimed ahead; 128 sources, 1 / 2 / 3 contexts, ms): 1280^2 0.617 / 0.538 / 0.561; 1536^2 0.771 /
-  // 0.741 / 0.772; 1792^2 0.933 / 0.956 / 1.005; 2048^2 1.106 / 1.189 / 1.233; 3072^2 (64 sources) 1.463 / 1.569 / 1.659; 4096^2 3.46 / 4.18 /
-  // 4.35; 1024^2 (256 sources) - / 0.624 / 0.608: three up to 1024, two up to 1664, one above.
-  const int maxdim = nx > ny ? nx : ny;
-  s.n_ctx = force_ctx > 0 ? force_ctx : (maxdim > 1664 ? 1 : maxdim > 1024 ? 2 : 3);
-  if (s.n_ctx > 16) s.n_ctx = 16;
-  for (;; --s.n_ctx) {
-    s.lds = (size_t)(anyw ? pool::make_layout(pool::kWavesAny, s.n_ctx, nx, ny, pool::kTStrideAny) : pool::make_layout(pool::kWaves, s.n_ctx, nx, ny)).total * 8;
-    if (s.lds <= kLdsLimit || s.n_ctx == 1) break;
-  }
-  return s;
-}
-
+// (what a launch decides -- contexts, heads, the first round: vhp_launch_plan.hpp; the sizes of its scratch: vhp_pool_scratch.hpp)
 template <typename OutT>
 hipError_t launch_pool_t(const BatchArgs& a) {
   using namespace pool;
   const bool anyw = pool_needs_anyw<OutT>(a.nx, a.field_stride > 0 ? a.field_stride : (long long)a.nx * a.ny, static_cast<const OutT*>(a.d_out));
   auto k = anyw ? vhp_pool_sweep<OutT, true> : vhp_pool_sweep<OutT, false>;
-  const PoolShape sh = pool_shape(a.nx, a.ny, a.pool_contexts, anyw);
-  const int waves = anyw ? kWavesAny : kWaves;
-  if (sh.lds > kLdsLimit || a.pool_epoch == 0) return hipErrorInvalidValue;
+  const PoolPlan p = plan_pool(a.nx, a.ny, a.n_src, a.n_cus, anyw, a.pool);
+  if (!p.ok || a.pool_epoch == 0) return hipErrorInvalidValue;
   if (a.raise_lds) {
-    hipError_t e = a.raise_lds(reinterpret_cast<const void*>(k), sh.lds);
+    hipError_t e = a.raise_lds(reinterpret_cast<const void*>(k), p.lds_bytes);
     if (e != hipSuccess) return e;
   }
   char* scratch = reinterpret_cast<char*>(a.d_queue);
   Args<OutT> g;
-  g.m.rows = a.rows; g.m.cols = a.cols; g.m.recip = a.recip;
-  g.m.wpr = a.wpr; g.m.wpc = a.wpc; g.m.nx = a.nx; g.m.ny = a.ny;
+  g.m = geom_map(a);
   g.out = static_cast<OutT*>(a.d_out);
   g.field_stride = a.field_stride;
   g.err_flag = a.d_err;
@@ -274,26 +217,19 @@ hipError_t launch_pool_t(const BatchArgs& a) {
   g.diag_stride = diag_stride_of(a.nx, a.ny);
   g.lines = reinterpret_cast<vhp::lanes::Tagged*>(scratch + head_bytes(a.n_src) + diag_bytes(a.n_src, a.nx, a.ny));
   g.epoch = a.pool_epoch;
-  g.busy_cap = a.pool_busy_cap > 0 ? a.pool_busy_cap : waves;
-  // two contexts take the largest units left, the others the smallest (0.75 against 0.78 ms with one head at 1000^2)
-  g.n_head = a.pool_heads > 0 ? a.pool_heads : (sh.n_ctx >= 3 ? 2 : 1);  // (all three from the head: 0.51 / 0.70 ms on two boxes, this: 0.53 / 0.67)
-  if (g.n_head > sh.n_ctx) g.n_head = sh.n_ctx;
-  g.tail_limit = (int)((long long)g.n_units * (a.pool_tail_pct > 0 ? a.pool_tail_pct : 15) / 100);  // (100 / 50 / 25 / 15 %: 0.56 / 0.55 / 0.53 / - and - / - / - / 0.67 ms on two boxes; round 4, with non-temporal stores: 5 / 15 / 30 / 60 %: 0.580 / 0.608 / 0.608 / 0.616 ms on a slow buffer, level on a fast one -- within the noise of 1-2 %)
-  g.early_ctx = a.pool_early_ctx > 0 ? a.pool_early_ctx : sh.n_ctx;
-  g.late_after = (int)((long long)g.n_units * (a.pool_late_pct > 0 ? a.pool_late_pct : 50) / 100);
-  // measured (tools/ab_slowfast.py, ab_libs.py; 0 / 16 / 32 / 48 / 64 steps): C3 on a fast buffer 0.485 / 0.468 / 0.463 / 0.461 / 0.460 ms, on a
-  // slow one 0.583 / 0.582 / 0.597 / 0.589 / 0.591 (bound by the memory there); C5 3.567 / 3.483 / 3.476 / 3.474 / 3.482; 128 sources at
-  // 2048^2 1.316 / - / 1.277 / - / 1.238; 512 at 512^2 0.445 / - / 0.419 / - / 0.416
-  g.claim_ahead = a.pool_claim_ahead >= 0 ? a.pool_claim_ahead : 48;
-  // the first unit of every context by workgroup index, the queue behind them (Args::static_round)
+  g.busy_cap = p.busy_cap;
+  g.n_head = p.n_head;
+  g.tail_limit = p.tail_limit;
+  g.early_ctx = p.early_ctx;
+  g.late_after = p.late_after;
+  g.claim_ahead = p.claim_ahead;
   g.n_groups = a.n_cus;
-  g.static_snake = a.pool_static_round >= 2;
-  g.static_round = a.pool_static_round != 0 && g.early_ctx >= sh.n_ctx && (long long)g.n_units >= (long long)sh.n_ctx * a.n_cus;
-  const unsigned long long queue0 = g.static_round ? ((unsigned long long)(g.n_head * a.n_cus) | ((unsigned long long)((sh.n_ctx - g.n_head) * a.n_cus) << 32)) : 0ull;
+  g.static_snake = p.static_snake;
+  g.static_round = p.static_round;
   if (a.ev_begin) (void)hipEventRecord(a.ev_begin, a.stream);  // the order pre-kernel is part of what a launch costs
   hipLaunchKernelGGL(vhp_pool_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, order, line_base, recs,
-                     line_blocks_per_source(a.nx, a.ny) * a.n_src, reinterpret_cast<unsigned long long*>(a.d_queue), queue0, a.d_err);
-  hipLaunchKernelGGL(k, dim3((unsigned)a.n_cus), dim3(64 * waves), sh.lds, a.stream, g, sh.n_ctx);
+                     line_blocks_per_source(a.nx, a.ny) * a.n_src, reinterpret_cast<unsigned long long*>(a.d_queue), p.queue0, a.d_err);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.n_cus), dim3(64 * p.waves), p.lds_bytes, a.stream, g, p.n_ctx);
   const hipError_t e = hipGetLastError();
   if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);
   return e;
@@ -303,12 +239,6 @@ hipError_t launch_pool_t(const BatchArgs& a) {
 size_t pool_scratch_bytes(int n_src, int nx, int ny) {
   return head_bytes(n_src) + diag_bytes(n_src, nx, ny) + (size_t)line_blocks_per_source(nx, ny) * (size_t)n_src * 64 * sizeof(vhp::lanes::Tagged);
 }
-
-bool pool_supported(int nx, int ny) {
-  if (nx <= 0 || ny <= 0 || nx > VHP_MAX_SIDE || ny > VHP_MAX_SIDE) return false;
-  return pool_shape(nx, ny, 0, false).lds <= kLdsLimit && pool_shape(nx, ny, 0, true).lds <= kLdsLimit;
-}
-
 
 #ifdef VHP_DIAG_TIMELINE
 extern "C" int vhp_debug_read_hist(unsigned long long* dst, int n_words) {

@@ -168,6 +168,24 @@ struct UnitGeo {
   VHP_FN int line_blocks() const { return n_strips > 1 ? (n_strips - 1) * nb : 0; }
 };
 
+// The bucket of a unit in the launch order (vhp_pool_order's counting sort; 0 = first).  Launch order = how early a unit has to start,
+// not how large it is: a unit is as long as its march (a thin octant along an axis is one strip, i.e. one wavefront, for 15 blocks:
+// sorted by cells it started last and the launch ended on it), so the key is mostly the march length; among equally long ones the
+// larger first.  inv_area = 1 / (nx ny), inv_side = 1 / max(nx, ny).  (g by value: behind a reference the callers' UnitGeo stays in
+// memory -- 40 bytes of scratch a lane in one of them, 36 KB of LDS in the other.)
+constexpr int kBuckets = 1024;
+VHP_FN int unit_launch_bucket(const UnitGeo g, double inv_area, double inv_side) {
+  double cells = 0.0;
+  if (g.n_strips > 0) {
+    if (g.x_major) { const double r = g.rows_total; cells = r * g.ni - r * (r - 1) * 0.5; }
+    else { const double c = g.cols_total; cells = c * (g.nj - 1) - c * (c - 1) * 0.5; }
+  }
+  const double march = (double)(g.x_major ? g.ni : g.nj) * inv_side;
+  double f = 0.8 * march + 0.2 * (cells * inv_area * 1.6 > 1.0 ? 1.0 : cells * inv_area * 1.6);
+  if (f > 1.0) f = 1.0;
+  return (kBuckets - 1) - (int)(f * (kBuckets - 1));
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The boundary line between a strip and its neighbours: what a strip reads from the strip below it and what it hands to
 // the strip above.  D = direction of the marching coordinate, c0 = the source's coordinate: step i is at c0 + D i.
