@@ -5,11 +5,12 @@ import shutil
 import subprocess
 import tempfile
 
+import cpu_driver
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "visibility-heuristic-path-planner_amd", "csrc")
 DRIVER = os.path.join(HERE, "pool_scratch_driver.cpp")
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 
 _exes = {}
 _dir = None
@@ -19,15 +20,11 @@ def driver(sanitized=False):
     """The driver's executable, plain or under the address and undefined-behaviour sanitizers; built once per process."""
     global _dir
     if sanitized not in _exes:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler (set CXX)"
         if _dir is None:
             _dir = tempfile.mkdtemp(prefix="pool_scratch_driver_")
             atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-        exe = os.path.join(_dir, "pool_scratch_driver" + ("_san" if sanitized else ""))
-        subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-DVHP_SIM"] + (SANITIZE if sanitized else ["-O2"])
-                              + ["-I", CSRC, "-o", exe, DRIVER])
-        _exes[sanitized] = exe
+        _exes[sanitized] = cpu_driver.build(DRIVER, _dir, "pool_scratch_driver" + ("_san" if sanitized else ""),
+                                            flags=("-Wno-unknown-pragmas", "-DVHP_SIM", "-O2"), includes=(CSRC,), sanitized=sanitized)
     return _exes[sanitized]
 
 

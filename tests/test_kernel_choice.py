@@ -10,11 +10,12 @@ Regenerate the table only when a crossover is meant to move:  python3 tests/test
 import itertools
 import json
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
+
+import cpu_driver
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -75,11 +76,7 @@ def key(row):
 
 
 def build_driver(out_dir, include=CSRC):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler (set CXX)"
-    exe = os.path.join(out_dir, "kernel_choice_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", include, "-o", exe, DRIVER])
-    return exe
+    return cpu_driver.build(DRIVER, out_dir, "kernel_choice_driver", flags=("-O1",), includes=(include,))
 
 
 def dump(exe):

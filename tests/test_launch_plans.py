@@ -23,18 +23,18 @@ Regenerate the table only when a launch is meant to change:  python3 tests/test_
 import itertools
 import json
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
+
+import cpu_driver
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "visibility-heuristic-path-planner_amd", "csrc")
 DRIVER = os.path.join(HERE, "launch_plan_driver.cpp")
 TABLE = os.path.join(HERE, "golden", "launch_plans.json")
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 
 CUS = (256, 80, 304)
 # contexts, claim_ahead, heads, tail_pct, early_ctx, late_pct, busy_cap, static_round: as vhp_set_option leaves them
@@ -125,12 +125,8 @@ def lat_request(nx, ny, n_src, n_cus=256, odd=0, asked=0, flags=("d_lat_order",)
 
 
 def build_driver(out_dir, include=CSRC, sanitized=False):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler (set CXX)"
-    exe = os.path.join(out_dir, "launch_plan_driver" + ("_san" if sanitized else ""))
-    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-DVHP_SIM"] + (SANITIZE if sanitized else ["-O1"])
-                          + ["-I", include, "-I", CSRC, "-o", exe, DRIVER])
-    return exe
+    return cpu_driver.build(DRIVER, out_dir, "launch_plan_driver" + ("_san" if sanitized else ""),
+                            flags=("-Wno-unknown-pragmas", "-DVHP_SIM", "-O1"), includes=(include, CSRC), sanitized=sanitized)
 
 
 def ask(exe, requests):

@@ -5,13 +5,13 @@ The driver is built twice: plain, and with the address and undefined-behaviour s
 header asks for); every case runs through both."""
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpu_driver
 import maps
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,15 +25,9 @@ OK, ERR_ARG, ERR_MAX_ITER, ERR_TOO_LARGE = 0, 1, 20, 102
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler (set CXX)"
     d = str(tmp_path_factory.mktemp("paths_driver"))
-    exes = []
-    for name, extra in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = os.path.join(d, "paths_driver_" + name)
-        subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off"] + extra + ["-I", CSRC, "-o", exe, DRIVER])
-        exes.append(exe)
-    return exes
+    return [cpu_driver.build(DRIVER, d, "paths_driver_" + name, flags=("-ffp-contract=off", "-O2"), includes=(CSRC,), sanitized=san)
+            for name, san in (("plain", False), ("san", True))]
 
 
 @pytest.fixture(scope="module")

@@ -6,11 +6,12 @@ once as it is and once with the address and undefined-behaviour sanitizers; both
 import itertools
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+import cpu_driver
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -29,13 +30,8 @@ LOOP_END = {20: "Max iters hit. Solution could not be found. Try lowering visibi
             3: "no cell reached the visibility threshold"}
 
 
-def build_driver(out_dir, name, extra=()):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler (set CXX)"
-    exe = os.path.join(out_dir, name)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           DRIVER])
-    return exe
+def build_driver(out_dir, name, sanitized=False):
+    return cpu_driver.build(DRIVER, out_dir, name, flags=("-O1",), includes=(CSRC, cpu_driver.INCLUDE), sanitized=sanitized)
 
 
 def ask(exe, lines):
@@ -106,6 +102,6 @@ def test_pivot_ints(driver):
 def test_driver_under_sanitizers(driver, tmp_path):
     # the stand-alone driver with the address and undefined-behaviour sanitizers (host code with its own main: nothing preloaded):
     # the same requests, the same answers, and a clean exit
-    san = build_driver(str(tmp_path), "planner_host_driver_san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    san = build_driver(str(tmp_path), "planner_host_driver_san", sanitized=True)
     lines = check_lines()[1] + ["status %d" % c for c in (0, 3, 20)] + ["scale 690 402", "scale 8192 8192", "pivots 0 0", "pivots 16777216 8"]
     assert ask(san, lines) == ask(driver, lines)

@@ -9,13 +9,13 @@ VHP_OK and at least a quarter have a path of three or more points (asserted; the
 oracle so that it holds: a solve stops when it sees its end, so only far-apart starts and ends light most of a map)."""
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpu_driver
 import maps
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,15 +30,9 @@ ALL = None   # goals: every cell of the grid
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler (set CXX)"
     d = str(tmp_path_factory.mktemp("tree_driver"))
-    exes = []
-    for name, extra in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = os.path.join(d, "tree_driver_" + name)
-        subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off"] + extra + ["-I", CSRC, "-o", exe, DRIVER])
-        exes.append(exe)
-    return exes
+    return [cpu_driver.build(DRIVER, d, "tree_driver_" + name, flags=("-ffp-contract=off", "-O2"), includes=(CSRC,), sanitized=san)
+            for name, san in (("plain", False), ("san", True))]
 
 
 @pytest.fixture(scope="module")

@@ -6,6 +6,7 @@
 
 #include <functional>
 
+#include "vhp_devbuf.hip.h"
 #include "vhp_launch_plan.hpp"
 
 namespace vhp {
@@ -15,10 +16,10 @@ struct PlannerDev;  // (vhp_planner_dev.hip.h)
 // The packed copies of n maps of one size (vhp_set_map: n = 1; vhp_set_maps: a stack, map k's words k strides after map 0's).
 struct PackedMaps {
   int n = 0, nx = 0, ny = 0, wpr = 0, wpc = 0;
-  uint64_t* rows = nullptr;   // packed along x: map k's words at rows + k * ny * wpr
-  uint64_t* cols = nullptr;   // packed along y: map k's at cols + k * nx * wpc
-  double* recip = nullptr;    // one reciprocal table for max(nx, ny)
-  uint64_t* dmap = nullptr;   // packed along both diagonals (lat_pack_diag_maps / lat_pack_diag_stack): what the latency sweep reads,
+  DevBuf<uint64_t> rows;      // packed along x: map k's words at rows + k * ny * wpr
+  DevBuf<uint64_t> cols;      // packed along y: map k's at cols + k * nx * wpc
+  DevBuf<double> recip;       // one reciprocal table for max(nx, ny)
+  DevBuf<uint64_t> dmap;      // packed along both diagonals (lat_pack_diag_maps / lat_pack_diag_stack): what the latency sweep reads,
                               // map k's lat_diag_map_bytes further; null where the latency sweep does not take the grid (or, for a
                               // stack, until the first planner batch on it builds them)
 };
@@ -66,7 +67,7 @@ struct BatchArgs {
 };
 
 inline void set_maps(BatchArgs& a, const PackedMaps& m) {
-  a.rows = m.rows; a.cols = m.cols; a.recip = m.recip; a.dmap = m.dmap;
+  a.rows = m.rows.get(); a.cols = m.cols.get(); a.recip = m.recip.get(); a.dmap = m.dmap.get();
   a.wpr = m.wpr; a.wpc = m.wpc; a.nx = m.nx; a.ny = m.ny;
   a.n_maps = m.n;
 }

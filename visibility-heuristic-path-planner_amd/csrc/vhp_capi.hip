@@ -39,28 +39,22 @@ struct vhp_ctx {
 
   int n_cus = 256;
   std::vector<void*> placed;   // buffers handed out by vhp_alloc_output
-  unsigned* d_probe_counter = nullptr;  // task counter of vhp_probe_stores
+  vhp::DevBuf<unsigned> d_probe_counter;  // task counter of vhp_probe_stores
   double last_alloc_ms = 0.0;  // what the last vhp_alloc_output cost: wall time of the search ...
   unsigned long long last_alloc_peak_bytes = 0;  // ... and the device memory it held at its peak (vhp_alloc_output_cost)
   int opt_alloc_budget_pct = 25;  // vhp_alloc_output: share of the free device memory its candidates may hold at once
   vhp::PackedMaps map;         // the map of vhp_set_map (n == 1): its packed copies, with the diagonal maps where the latency sweep takes the grid
-  uint8_t* d_occ = nullptr;    // ... its uint8 form (kept for the planner's validation and packing)
+  vhp::DevBuf<uint8_t> d_occ;  // ... its uint8 form (kept for the planner's validation and packing)
   std::vector<uint8_t> h_occ;  // ... and that one's host copy when vhp_set_map brought it (empty after vhp_set_map_device)
-  int* d_err = nullptr;
+  vhp::DevBuf<int> d_err;
 
-  // grow-only scratch (grow), capacities in bytes; first the host-buffer sweep entry points' (stage_batch)
-  int32_t* d_src = nullptr;
-  size_t d_src_cap = 0;
-  void* d_out = nullptr;
-  size_t d_out_cap = 0;
-  double* d_bnd = nullptr;  // boundary rows of multi-round sweeps (sides above W*64*R)
-  size_t d_bnd_cap = 0;
-  int* d_order = nullptr;   // launch order of the (source, quadrant) units (+ one int4 descriptor per workgroup)
-  size_t d_order_cap = 0;
-  int* d_lat_order = nullptr;  // launch order of the latency sweep's units where it launches more of them than the device has CUs
-  size_t d_lat_order_cap = 0;
-  int* d_pool = nullptr;    // pool sweep: pull counter, unit order, diagonal lines, tagged boundary lines (zeroed when allocated)
-  size_t d_pool_cap = 0;
+  // grow-only scratch (vhp_devbuf.hpp: a failed grow leaves an empty buffer); first the host-buffer sweep entry points' (stage_batch)
+  vhp::DevBuf<int32_t> d_src;
+  vhp::DevBuf<void> d_out;
+  vhp::DevBuf<double> d_bnd;     // boundary rows of multi-round sweeps (sides above W*64*R)
+  vhp::DevBuf<int> d_order;      // launch order of the (source, quadrant) units (+ one int4 descriptor per workgroup)
+  vhp::DevBuf<int> d_lat_order;  // launch order of the latency sweep's units where it launches more of them than the device has CUs
+  vhp::DevBuf<int> d_pool;       // pool sweep: pull counter, unit order, diagonal lines, tagged boundary lines (zeroed when allocated)
   unsigned long long pool_epoch = 0x5A17000000000000ull;  // tag of the last pool launch
   bool timing = false;      // per-launch event pairs around the sweep kernel (vhp_timing)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> timed_launches;
@@ -87,8 +81,7 @@ struct vhp_ctx {
   // the stack of maps of vhp_set_maps (vhp_sweep_maps_batch): state of its own, apart from the single map above; its diagonal maps are
   // built by the first planner batch on the stack that takes the latency sweep (vhp_planner_solve_maps_batch) and kept until the stack goes
   vhp::PackedMaps maps;
-  int32_t* d_map_idx = nullptr;     // host-buffer form's slice of map indices (grow)
-  size_t d_map_idx_cap = 0;
+  vhp::DevBuf<int32_t> d_map_idx;   // host-buffer form's slice of map indices (grow-only)
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
   vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
@@ -143,9 +136,9 @@ int fail(vhp_ctx* c, int code, const std::string& msg) {
 // Map 0 of p; a sweep on a stack moves to map k by k times maps_stack's strides.
 vhp::DevMap dev_map(const vhp::PackedMaps& p) {
   vhp::DevMap m;
-  m.rows = p.rows;
-  m.cols = p.cols;
-  m.recip = p.recip;
+  m.rows = p.rows.get();
+  m.cols = p.cols.get();
+  m.recip = p.recip.get();
   m.wpr = p.wpr;
   m.wpc = p.wpc;
   m.nx = p.nx;
@@ -160,26 +153,19 @@ vhp::MapStack maps_stack(const vhp::PackedMaps& p, const int32_t* d_map_idx) {
   return {d_map_idx, p.n, (long long)p.ny * p.wpr, (long long)p.nx * p.wpc};
 }
 
-void free_packed(vhp::PackedMaps& p) {
-  for (void* q : {(void*)p.rows, (void*)p.cols, (void*)p.recip, (void*)p.dmap})
-    if (q) (void)hipFree(q);
-  p = vhp::PackedMaps{};
-}
-
 void free_map(vhp_ctx* c) {
-  if (c->d_occ) hipFree(c->d_occ);
-  c->d_occ = nullptr;
-  free_packed(c->map);
+  c->d_occ.reset();
+  c->map = vhp::PackedMaps{};
   c->h_occ.clear();
   c->pl.h_occ = nullptr;
   vhp::planner_free(c->pl);
-  vhp::spec_free(c->spec);
+  c->spec = vhp::SpecState{};
   vhp::batch_free(c->batch);
-  vhp::queue_scratch_free(c->qs);
+  c->qs = vhp::QueueScratch{};
 }
 
 void free_maps(vhp_ctx* c) {
-  free_packed(c->maps);
+  c->maps = vhp::PackedMaps{};
   vhp::batch_free(c->maps_batch);
 }
 
@@ -193,19 +179,6 @@ std::vector<double> recip_table(int nx, int ny) {
     recip[k] = 1.0 / d;  // correctly rounded IEEE division on the host
   }
   return recip;
-}
-
-// Grow-only device scratch: reallocated (contents not kept) when `bytes` exceeds its capacity, zeroed when new if `zero`.
-template <typename T>
-hipError_t grow(T** p, size_t* cap_bytes, size_t bytes, bool zero, hipStream_t stream) {
-  if (*cap_bytes >= bytes) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap_bytes = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess && zero) e = hipMemsetAsync(*p, 0, bytes, stream);
-  if (e == hipSuccess) *cap_bytes = bytes;
-  return e;
 }
 
 // How an internal launch writes its fields and whether vhp_timing times it.  The entry point passes it down; nothing parks it on the
@@ -259,7 +232,7 @@ vhp::SweepPlan plan_for_maps(const vhp_ctx* c, int n_src, bool f64) { return pla
 // The planner's sweeps of n_src sources: the plan, and the front sweep's shape and round scratch (n_workgroups) from it.
 hipError_t plan_planner(vhp_ctx* ctx, vhp::DevMap& pm, int n_src, size_t n_workgroups, vhp::SweepPlan* plan) {
   *plan = plan_for(ctx, n_src, true);
-  hipError_t e = vhp::attach_round_scratch(pm, plan->W * 64 * plan->R, n_workgroups, &ctx->d_bnd, &ctx->d_bnd_cap);
+  hipError_t e = vhp::attach_round_scratch(pm, plan->W * 64 * plan->R, n_workgroups, ctx->d_bnd);
   if (e != hipSuccess) return e;
   ctx->pl.R = plan->R;
   ctx->pl.W = plan->W;
@@ -286,7 +259,7 @@ hipError_t launch_sweep_t(vhp_ctx* c, const vhp::PackedMaps& pm, const int32_t* 
   vhp::DevMap m = dev_map(pm);
   const long long stride = o.field_stride > 0 ? o.field_stride : (long long)m.nx * m.ny;
   m.slide = plan.slide;
-  hipError_t eb = vhp::attach_round_scratch(m, W * 64 * R, (size_t)n_src * vhp::kUnitsPerSource, &c->d_bnd, &c->d_bnd_cap);
+  hipError_t eb = vhp::attach_round_scratch(m, W * 64 * R, (size_t)n_src * vhp::kUnitsPerSource, c->d_bnd);
   if (eb != hipSuccess) return eb;
   const size_t n_units = (size_t)n_src * vhp::kUnitsPerSource;
   const int* order = nullptr;
@@ -296,10 +269,10 @@ hipError_t launch_sweep_t(vhp_ctx* c, const vhp::PackedMaps& pm, const int32_t* 
   if (hipError_t ee = acquire_events(c, o.timed, &ev); ee != hipSuccess) return ee;
   if (ev.first) (void)hipEventRecord(ev.first, c->stream);
   if (n_src >= 8) {  // worth a 1-workgroup pre-kernel once the batch spans many CUs
-    hipError_t eo = grow(&c->d_order, &c->d_order_cap, n_units * (sizeof(int) + sizeof(int4)) + 16, false, c->stream);
+    hipError_t eo = c->d_order.grow(n_units * (sizeof(int) + sizeof(int4)) + 16);
     if (eo != hipSuccess) { release_events(c, ev, eo); return eo; }
-    int4* d_desc = reinterpret_cast<int4*>(c->d_order);                      // n_units descriptors first (16-byte aligned)
-    int* d_ord = reinterpret_cast<int*>(d_desc + n_units);                   // then the order list
+    int4* d_desc = reinterpret_cast<int4*>(c->d_order.get());  // n_units descriptors first (16-byte aligned)
+    int* d_ord = reinterpret_cast<int*>(d_desc + n_units);     // then the order list
     // Packing short quadrants into one workgroup is implemented and parity-tested, but measured slower
     // on MI355X: off unless VHP_PACK is set.
     const int pack_w = (!MULTI && W == 8 && pack) ? W : 0;
@@ -309,8 +282,8 @@ hipError_t launch_sweep_t(vhp_ctx* c, const vhp::PackedMaps& pm, const int32_t* 
     desc = d_desc;
   }
   const unsigned grid = (unsigned)n_units;
-  if (stack) hipLaunchKernelGGL(km, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, *stack, d_out, stride, c->d_err, order, desc);
-  else hipLaunchKernelGGL(k, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, d_out, stride, c->d_err, order, desc);
+  if (stack) hipLaunchKernelGGL(km, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, *stack, d_out, stride, c->d_err.get(), order, desc);
+  else hipLaunchKernelGGL(k, dim3(grid), dim3(128 * W), lds, c->stream, m, d_src, d_out, stride, c->d_err.get(), order, desc);
   const hipError_t el = hipGetLastError();
   if (ev.first) (void)hipEventRecord(ev.second, c->stream);
   release_events(c, ev, el);
@@ -324,20 +297,24 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const vhp::PackedMaps& m, const int32_
                               const vhp::LatLaunch& l = {}) {
   // (the scratch is an allocation of its own: nothing but these two kernels may write the tagged lines)
   const size_t scratch = lat ? vhp::lat_scratch_bytes(n_src, m.nx, m.ny) : vhp::pool_scratch_bytes(n_src, m.nx, m.ny);
-  if (hipError_t eo = grow(&c->d_pool, &c->d_pool_cap, scratch, true, c->stream); eo != hipSuccess) return eo;
+  if (c->d_pool.bytes() < scratch) {  // (zero when it is first used; the memset goes on the context's stream)
+    hipError_t eo = c->d_pool.grow(scratch);
+    if (eo == hipSuccess) eo = hipMemsetAsync(c->d_pool.get(), 0, scratch, c->stream);
+    if (eo != hipSuccess) { c->d_pool.reset(); return eo; }
+  }
   vhp::BatchArgs a;
   vhp::set_maps(a, m);
   a.d_src = d_src; a.n_src = n_src; a.d_out = d_out;
   a.dtype = sizeof(OutT) == 8 ? VHP_F64 : VHP_F32;
   a.field_stride = o.field_stride > 0 ? o.field_stride : (long long)m.nx * m.ny;
-  a.d_err = c->d_err;
-  a.d_queue = c->d_pool;
+  a.d_err = c->d_err.get();
+  a.d_queue = c->d_pool.get();
   a.pool_epoch = ++c->pool_epoch;
   a.lat = l;
   a.lat_workgroups = c->opt_lat_workgroups;
   if (lat)
-    if (hipError_t eo = grow(&c->d_lat_order, &c->d_lat_order_cap, vhp::lat_order_bytes(), false, c->stream); eo != hipSuccess) return eo;
-  a.d_lat_order = c->d_lat_order;
+    if (hipError_t eo = c->d_lat_order.grow(vhp::lat_order_bytes()); eo != hipSuccess) return eo;
+  a.d_lat_order = c->d_lat_order.get();
   a.n_cus = c->n_cus;
   a.stream = c->stream;
   a.raise_lds = [c](const void* fn, size_t bytes) { return raise_lds_limit(c, fn, bytes); };
@@ -398,15 +375,15 @@ int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src
   if (n_src == 0) return VHP_OK;
   VHP_ON_DEVICE(ctx);
   const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / field));
-  hipError_t e = grow(&ctx->d_src, &ctx->d_src_cap, (size_t)slice * 2 * sizeof(int32_t), false, ctx->stream);
-  if (e == hipSuccess) e = grow(&ctx->d_out, &ctx->d_out_cap, (size_t)slice * field, false, ctx->stream);
+  hipError_t e = ctx->d_src.grow((size_t)slice * 2 * sizeof(int32_t));
+  if (e == hipSuccess) e = ctx->d_out.grow((size_t)slice * field);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
   for (int s0 = 0; s0 < n_src; s0 += slice) {
     const int n = std::min(slice, n_src - s0);
-    VHP_HIP(hipMemcpyAsync(ctx->d_src, src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    VHP_HIP(hipMemcpyAsync(ctx->d_src.get(), src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     const int rc = launch(s0, n);
     if (rc != VHP_OK) return rc;
-    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * field, ctx->d_out, (size_t)n * field, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * field, ctx->d_out.get(), (size_t)n * field, hipMemcpyDeviceToHost, ctx->stream));
     VHP_HIP(hipStreamSynchronize(ctx->stream));
   }
   return VHP_OK;
@@ -414,20 +391,20 @@ int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src
 
 // The packed copies of n maps of nx x ny into m: allocated and zeroed, packed by pack(wpr, wpc, row_blocks, col_blocks) -- the caller's
 // kernels on the context's stream, blocks of 256 threads for one map's words --, the reciprocal table uploaded, and the sizes recorded
-// once all of it is on the device.  On failure the caller frees what was built.
+// once all of it is on the device.  m comes in empty; on failure the caller drops what was built.
 template <typename Pack>
 int build_packed(vhp_ctx* ctx, vhp::PackedMaps& m, int n, int nx, int ny, Pack pack) {
   const int wpr = (nx + 63) / 64 + 2, wpc = (ny + 63) / 64 + 2;
   const size_t rows_words = (size_t)n * ny * wpr, cols_words = (size_t)n * nx * wpc;
-  VHP_HIP(hipMalloc(&m.rows, rows_words * 8));
-  VHP_HIP(hipMalloc(&m.cols, cols_words * 8));
-  VHP_HIP(hipMemsetAsync(m.rows, 0, rows_words * 8, ctx->stream));
-  VHP_HIP(hipMemsetAsync(m.cols, 0, cols_words * 8, ctx->stream));
+  VHP_HIP(m.rows.grow(rows_words * 8));
+  VHP_HIP(m.cols.grow(cols_words * 8));
+  VHP_HIP(hipMemsetAsync(m.rows.get(), 0, rows_words * 8, ctx->stream));
+  VHP_HIP(hipMemsetAsync(m.cols.get(), 0, cols_words * 8, ctx->stream));
   const unsigned row_blocks = (unsigned)(((long long)(wpr - 2) * ny * 64 + 255) / 256), col_blocks = (unsigned)(((long long)(wpc - 2) * nx * 64 + 255) / 256);
   if (const int rc = pack(wpr, wpc, row_blocks, col_blocks); rc != VHP_OK) return rc;
   const std::vector<double> recip = recip_table(nx, ny);
-  VHP_HIP(hipMalloc(&m.recip, recip.size() * sizeof(double)));
-  VHP_HIP(hipMemcpyAsync(m.recip, recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(m.recip.grow(recip.size() * sizeof(double)));
+  VHP_HIP(hipMemcpyAsync(m.recip.get(), recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   m.n = n; m.nx = nx; m.ny = ny; m.wpr = wpr; m.wpc = wpc;
   return VHP_OK;
@@ -437,15 +414,15 @@ int build_packed(vhp_ctx* ctx, vhp::PackedMaps& m, int n, int nx, int ny, Pack p
 int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
   vhp::PackedMaps& m = ctx->map;
   return build_packed(ctx, m, 1, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
-    hipLaunchKernelGGL(vhp::vhp_pack_rows, dim3(row_blocks), dim3(256), 0, ctx->stream, ctx->d_occ, m.rows, nx, ny, wpr);
+    hipLaunchKernelGGL(vhp::vhp_pack_rows, dim3(row_blocks), dim3(256), 0, ctx->stream, ctx->d_occ.get(), m.rows.get(), nx, ny, wpr);
     VHP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(col_blocks), dim3(256), 0, ctx->stream, ctx->d_occ, m.cols, nx, ny, wpc);
+    hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(col_blocks), dim3(256), 0, ctx->stream, ctx->d_occ.get(), m.cols.get(), nx, ny, wpc);
     VHP_HIP(hipGetLastError());
     if (vhp::lat_supported(nx, ny)) {
       const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
-      VHP_HIP(hipMalloc(&m.dmap, bytes));
-      VHP_HIP(hipMemsetAsync(m.dmap, 0, bytes, ctx->stream));
-      VHP_HIP(vhp::lat_pack_diag_maps(ctx->d_occ, nx, ny, m.dmap, ctx->stream));
+      VHP_HIP(m.dmap.grow(bytes));
+      VHP_HIP(hipMemsetAsync(m.dmap.get(), 0, bytes, ctx->stream));
+      VHP_HIP(vhp::lat_pack_diag_maps(ctx->d_occ.get(), nx, ny, m.dmap.get(), ctx->stream));
     }
     return VHP_OK;
   });
@@ -453,20 +430,20 @@ int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
 
 // The stack of vhp_set_maps from the n_maps uint8 maps at src (host or device): both packed copies of every map, one launch each.
 int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, bool from_device) {
-  struct Staged { uint8_t* p = nullptr; ~Staged() { if (p) (void)hipFree(p); } } staged;  // the host maps' device copy, for the packing only
+  vhp::DevBuf<uint8_t> staged;  // the host maps' device copy, for the packing only
   const size_t cells = (size_t)n_maps * nx * ny;
   const uint8_t* d_occ = src;
   if (!from_device) {
-    VHP_HIP(hipMalloc(&staged.p, cells));
-    VHP_HIP(hipMemcpyAsync(staged.p, src, cells, hipMemcpyHostToDevice, ctx->stream));
-    d_occ = staged.p;
+    VHP_HIP(staged.grow(cells));
+    VHP_HIP(hipMemcpyAsync(staged.get(), src, cells, hipMemcpyHostToDevice, ctx->stream));
+    d_occ = staged.get();
   }
   vhp::PackedMaps& m = ctx->maps;
   return build_packed(ctx, m, n_maps, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
     const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernels step through more maps than that)
-    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.rows, n_maps, nx, ny, wpr);
+    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.rows.get(), n_maps, nx, ny, wpr);
     VHP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.cols, n_maps, nx, ny, wpc);
+    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.cols.get(), n_maps, nx, ny, wpc);
     VHP_HIP(hipGetLastError());
     return VHP_OK;
   });
@@ -524,7 +501,7 @@ void note_unsolved(vhp_ctx* ctx, int rc) {
 template <typename Solve>
 int planner_call(vhp_ctx* ctx, const char* who, int n_src, size_t n_workgroups, Solve solve) {
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no map set");
   VHP_ON_DEVICE(ctx);
   std::string msg;
   vhp::DevMap pm = dev_map(ctx->map);
@@ -542,11 +519,11 @@ int planner_call(vhp_ctx* ctx, const char* who, int n_src, size_t n_workgroups, 
 // What a path call reads of the last batch on b (nx x ny): every query's slot or validation code, its n_pivots, the slots' arrays.
 vhp::PathsDev batch_paths_dev(const vhp::BatchState& b, const std::vector<int32_t>& codes, int nx, int ny) {
   vhp::PathsDev p{};
-  p.label = b.label;
-  p.pivots = b.pivots;
+  p.label = b.label.get();
+  p.pivots = b.pivots.get();
   p.label_stride = b.cells;
   p.pivot_stride = b.pivot_stride;
-  p.query = b.query;
+  p.query = b.query.get();
   p.nx = nx;
   p.ny = ny;
   p.n_queries = (int)b.slot_of.size();
@@ -562,8 +539,8 @@ vhp::PathsDev batch_paths_dev(const vhp::BatchState& b, const std::vector<int32_
 vhp::PathsDev plain_paths_dev(const vhp_ctx* ctx) {
   const vhp::PlannerState& s = ctx->pl;
   vhp::PathsDev p{};
-  p.label = s.label;
-  p.pivots = s.pivots;
+  p.label = s.label.get();
+  p.pivots = s.pivots.get();
   p.query = nullptr;
   p.end_x = s.last_end_x;
   p.end_y = s.last_end_y;
@@ -688,8 +665,8 @@ int vhp_create(int device_ordinal, vhp_ctx** out) {
   DeviceGuard guard(device_ordinal);
   if (!guard.ok || hipStreamCreate(&ctx->own_stream) != hipSuccess ||
       create_timing_event(&ctx->ev0) != hipSuccess || create_timing_event(&ctx->ev1) != hipSuccess ||
-      hipMalloc(&ctx->d_err, sizeof(int)) != hipSuccess || hipMemset(ctx->d_err, 0, sizeof(int)) != hipSuccess) {
-    delete ctx;
+      ctx->d_err.grow(sizeof(int)) != hipSuccess || hipMemset(ctx->d_err.get(), 0, sizeof(int)) != hipSuccess) {
+    delete ctx;  // (on its device: the guard is still in scope)
     return VHP_ERR_HIP;
   }
   ctx->stream = ctx->own_stream;
@@ -707,19 +684,13 @@ int vhp_destroy(vhp_ctx* ctx) {
   hipStreamSynchronize(ctx->stream);
   free_map(ctx);
   free_maps(ctx);
-  vhp::paths_free(ctx->paths);
-  vhp::tree_free(ctx->tree);
-  for (void* p : {(void*)ctx->d_src, (void*)ctx->d_map_idx, ctx->d_out, (void*)ctx->d_bnd, (void*)ctx->d_order, (void*)ctx->d_lat_order, (void*)ctx->d_pool})
-    if (p) (void)hipFree(p);
   for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto& pr : ctx->event_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (ctx->d_err) hipFree(ctx->d_err);
   for (void* p : ctx->placed) (void)hipFree(p);
-  if (ctx->d_probe_counter) (void)hipFree(ctx->d_probe_counter);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;  // (its buffers go here, on the context's device: the guard is still in scope)
   return VHP_OK;
 }
 
@@ -739,8 +710,8 @@ static int set_map_common(vhp_ctx* ctx, const uint8_t* src, int nx, int ny, bool
   free_map(ctx);
   ctx->opt_field_stride = 0;  // (a stride belongs to a grid: one left over from a smaller grid would make the fields overlap)
   const size_t n = (size_t)nx * ny;
-  VHP_HIP(hipMalloc(&ctx->d_occ, n));
-  VHP_HIP(hipMemcpyAsync(ctx->d_occ, src, n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(ctx->d_occ.grow(n));
+  VHP_HIP(hipMemcpyAsync(ctx->d_occ.get(), src, n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
   ctx->h_occ.clear();
   ctx->pl.h_occ = nullptr;
   const int rc = finish_set_map(ctx, nx, ny);
@@ -759,7 +730,7 @@ int vhp_set_map_device(vhp_ctx* ctx, const uint8_t* d_occ, int nx, int ny) { ret
 // vhp_sweep_batch_device writing its fields o.field_stride apart (the entry point: the option; the host-buffer form: packed)
 static int sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int variant, int dtype, void* d_out, const LaunchOpts& o) {
   if (!ctx || !d_src_xy || !d_out || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: bad argument");
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_device: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_device: no map set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   if (variant != VHP_SWEEP_FULL && variant != VHP_SWEEP_QUEUE) return fail(ctx, VHP_ERR_ARG, "bad variant");
   // (any alignment of whole elements is swept -- the kernels' builds for fields off the 16-byte grid --, a pointer inside an element is not)
@@ -773,7 +744,7 @@ static int sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, 
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   hipError_t e;
   if (variant == VHP_SWEEP_QUEUE) {
-    e = vhp::launch_queue_sweep_impl(ctx->qs, dev_map(ctx->map), ctx->d_occ, d_src_xy, n_src, dtype, d_out, ctx->d_err, ctx->stream);
+    e = vhp::launch_queue_sweep_impl(ctx->qs, dev_map(ctx->map), ctx->d_occ.get(), d_src_xy, n_src, dtype, d_out, ctx->d_err.get(), ctx->stream);
   } else if (dtype == VHP_F64) {
     e = launch_sweep<double>(ctx, d_src_xy, n_src, static_cast<double*>(d_out), o);
   } else {
@@ -794,9 +765,9 @@ int vhp_sync(vhp_ctx* ctx) {
   VHP_ON_DEVICE(ctx);
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   int flag = 0;
-  VHP_HIP(hipMemcpy(&flag, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost));
+  VHP_HIP(hipMemcpy(&flag, ctx->d_err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (flag) {
-    VHP_HIP(hipMemset(ctx->d_err, 0, sizeof(int)));
+    VHP_HIP(hipMemset(ctx->d_err.get(), 0, sizeof(int)));
     return fail(ctx, VHP_ERR_SOURCE_OOB, "a sweep source lies outside the grid");
   }
   return VHP_OK;
@@ -804,11 +775,11 @@ int vhp_sync(vhp_ctx* ctx) {
 
 int vhp_sweep_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int variant, int dtype, void* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch: bad argument");
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch: no map set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   // (the library's own scratch holds packed fields and is copied out packed: "field_stride" is a property of a caller's device buffer)
   const int rc = stage_batch(ctx, "vhp_sweep_batch", src_xy, n_src, dtype == VHP_F64 ? 8 : 4, out_host,
-                             [&](int n) { return sweep_batch_device(ctx, ctx->d_src, n, variant, dtype, ctx->d_out, {0, ctx->timing}); });
+                             [&](int n) { return sweep_batch_device(ctx, ctx->d_src.get(), n, variant, dtype, ctx->d_out.get(), {0, ctx->timing}); });
   return rc == VHP_OK && n_src > 0 ? vhp_sync(ctx) : rc;
 }
 
@@ -830,7 +801,7 @@ int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, 
 static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out,
                                    const LaunchOpts& o) {
   if (!ctx || !d_src_xy || !d_map_idx || !d_out || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: bad argument");
-  if (!ctx->maps.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch_device: no maps set");
+  if (!ctx->maps.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch_device: no maps set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   if (reinterpret_cast<uintptr_t>(d_out) % (dtype == VHP_F64 ? 8 : 4) != 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch_device: d_out is not aligned to its element type");
   if (o.field_stride > 0 && o.field_stride < (long long)ctx->maps.nx * ctx->maps.ny)
@@ -852,14 +823,14 @@ int vhp_sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int
 
 int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host) {
   if (!ctx || !src_xy || !map_idx || !out_host || n_src < 0) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_maps_batch: bad argument");
-  if (!ctx->maps.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch: no maps set");
+  if (!ctx->maps.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_maps_batch: no maps set");
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   const size_t field = (size_t)ctx->maps.nx * ctx->maps.ny * (dtype == VHP_F64 ? 8 : 4);
   int rc = stage_slices(ctx, "vhp_sweep_maps_batch", src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
-    const hipError_t e = grow(&ctx->d_map_idx, &ctx->d_map_idx_cap, (size_t)n * sizeof(int32_t), false, ctx->stream);
+    const hipError_t e = ctx->d_map_idx.grow((size_t)n * sizeof(int32_t));
     if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_sweep_maps_batch: scratch: ") + hipGetErrorString(e));
-    VHP_HIP(hipMemcpyAsync(ctx->d_map_idx, map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    return sweep_maps_batch_device(ctx, ctx->d_src, ctx->d_map_idx, n, dtype, ctx->d_out, {0, ctx->timing});
+    VHP_HIP(hipMemcpyAsync(ctx->d_map_idx.get(), map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return sweep_maps_batch_device(ctx, ctx->d_src.get(), ctx->d_map_idx.get(), n, dtype, ctx->d_out.get(), {0, ctx->timing});
   });
   if (rc != VHP_OK || n_src == 0) return rc;
   rc = vhp_sync(ctx);
@@ -874,16 +845,16 @@ int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map
 
 int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
   if (!ctx || !out_host) return fail(ctx, VHP_ERR_ARG, "vhp_raycast_all: bad argument");
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_raycast_all: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_raycast_all: no map set");
   if (src_x < 0 || src_y < 0 || src_x >= ctx->map.nx || src_y >= ctx->map.ny) return fail(ctx, VHP_ERR_SOURCE_OOB, "source outside the grid");
   VHP_ON_DEVICE(ctx);
   const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
-  VHP_HIP(grow(&ctx->d_out, &ctx->d_out_cap, cells * 8, false, ctx->stream));
-  double* d = static_cast<double*>(ctx->d_out);
+  VHP_HIP(ctx->d_out.grow(cells * 8));
+  double* d = static_cast<double*>(ctx->d_out.get());
   const unsigned blocks = (unsigned)((cells + 255) / 256);
   VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   hipLaunchKernelGGL(vhp::vhp_fill_f64, dim3(blocks), dim3(256), 0, ctx->stream, d, 1.0, cells);
-  hipLaunchKernelGGL(vhp::vhp_raycast, dim3(blocks), dim3(256), 0, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, src_x, src_y, d);
+  hipLaunchKernelGGL(vhp::vhp_raycast, dim3(blocks), dim3(256), 0, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ.get(), src_x, src_y, d);
   VHP_HIP(hipGetLastError());
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
@@ -927,23 +898,23 @@ static int variant_launch_sweep(vhp_ctx* ctx, const int32_t* d_src, int n_src, d
   auto k = vhp::variant::vhp_variant_sweep;
   hipError_t e = raise_lds_limit(ctx, reinterpret_cast<const void*>(k), lds);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("variant sweep: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(k, dim3((unsigned)(4 * n_src)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, d_src, d_out,
-                     (long long)ctx->map.nx * ctx->map.ny, alpha, fac, ctx->d_err);
+  hipLaunchKernelGGL(k, dim3((unsigned)(4 * n_src)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ.get(), d_src, d_out,
+                     (long long)ctx->map.nx * ctx->map.ny, alpha, fac, ctx->d_err.get());
   VHP_HIP(hipGetLastError());
   return VHP_OK;
 }
 
 int vhp_sweep_batch_variant(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double alpha, double fac, double* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(fac > 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_variant: bad argument");
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_variant: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_variant: no map set");
   if (std::max(ctx->map.nx, ctx->map.ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant sweeps: grid side above 4096");
   return stage_batch(ctx, "vhp_sweep_batch_variant", src_xy, n_src, 8, out_host,
-                     [&](int n) { return variant_launch_sweep(ctx, ctx->d_src, n, alpha, fac, static_cast<double*>(ctx->d_out)); });
+                     [&](int n) { return variant_launch_sweep(ctx, ctx->d_src.get(), n, alpha, fac, static_cast<double*>(ctx->d_out.get())); });
 }
 
 int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double offset, double* out_host) {
   if (!ctx || !src_xy || !out_host || n_src < 0 || !(offset >= 0)) return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_offset: bad argument");
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_offset: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_sweep_batch_offset: no map set");
   if (std::max(ctx->map.nx, ctx->map.ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "offset sweeps: grid side above 4096");
   const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
   const size_t lds = (size_t)3 * (std::max(ctx->map.nx, ctx->map.ny) + 1) * sizeof(double);
@@ -955,9 +926,9 @@ int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, doubl
       if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("offset sweep: ") + hipGetErrorString(e));
       raised = true;
     }
-    VHP_HIP(hipMemsetAsync(ctx->d_out, 0, (size_t)n * cells * 8, ctx->stream));  // a freshly reset() solver
-    hipLaunchKernelGGL(k, dim3((unsigned)(4 * n)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ, ctx->d_src,
-                       static_cast<double*>(ctx->d_out), (long long)cells, offset, ctx->d_err);
+    VHP_HIP(hipMemsetAsync(ctx->d_out.get(), 0, (size_t)n * cells * 8, ctx->stream));  // a freshly reset() solver
+    hipLaunchKernelGGL(k, dim3((unsigned)(4 * n)), dim3(1024), lds, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ.get(), ctx->d_src.get(),
+                       static_cast<double*>(ctx->d_out.get()), (long long)cells, offset, ctx->d_err.get());
     VHP_HIP(hipGetLastError());
     return VHP_OK;
   });
@@ -968,7 +939,7 @@ int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x,
                               uint32_t* n_waypoints) {
   using namespace vhp::variant;
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->map.rows) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_variant: no map set");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_planner_solve_variant: no map set");
   const int nx = ctx->map.nx, ny = ctx->map.ny;
   if (std::max(nx, ny) > 4096) return fail(ctx, VHP_ERR_TOO_LARGE, "variant planner: grid side above 4096");
   if ((unsigned)start_x >= (unsigned)nx || (unsigned)start_y >= (unsigned)ny) return fail(ctx, VHP_ERR_START_OOB, "Start point is out of bounds.");
@@ -976,60 +947,55 @@ int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x,
   if (max_iter > (1u << 20)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
   VHP_ON_DEVICE(ctx);
   const size_t cells = (size_t)nx * ny;
-  double *d_uni = nullptr, *d_loc = nullptr;
-  uint32_t* d_lab = nullptr;
-  unsigned long long* d_lab64 = nullptr;
-  int32_t* d_way = nullptr;
-  PlannerCtl* d_ctl = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_uni, (void*)d_loc, (void*)d_lab, (void*)d_lab64, (void*)d_way, (void*)d_ctl})
-      if (p) (void)hipFree(p);
-  };
-#define VHP_V(call)                                                                      \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) { cleanup(); return fail(ctx, VHP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } \
-  } while (0)
-  VHP_V(hipMalloc(&d_uni, cells * 8));
-  VHP_V(hipMalloc(&d_loc, cells * 8));
-  VHP_V(hipMalloc(&d_lab, cells * 4));
-  VHP_V(hipMalloc(&d_lab64, cells * 8));
-  VHP_V(hipMalloc(&d_way, 2 * (size_t)(max_iter + 3) * sizeof(int32_t)));
-  VHP_V(hipMalloc(&d_ctl, sizeof(PlannerCtl)));
-  VHP_V(hipMemsetAsync(d_uni, 0, cells * 8, ctx->stream));
-  VHP_V(hipMemsetAsync(d_lab, 0xff, cells * 4, ctx->stream));
+  // (the solve's own state, gone however the function is left)
+  vhp::DevBuf<double> uni, loc;
+  vhp::DevBuf<uint32_t> lab;
+  vhp::DevBuf<unsigned long long> lab64;
+  vhp::DevBuf<int32_t> way;
+  vhp::DevBuf<PlannerCtl> ctl;
+  VHP_HIP(uni.grow(cells * 8));
+  VHP_HIP(loc.grow(cells * 8));
+  VHP_HIP(lab.grow(cells * 4));
+  VHP_HIP(lab64.grow(cells * 8));
+  VHP_HIP(way.grow(2 * (size_t)(max_iter + 3) * sizeof(int32_t)));
+  VHP_HIP(ctl.grow(sizeof(PlannerCtl)));
+  double *const d_uni = uni.get(), *const d_loc = loc.get();
+  uint32_t* const d_lab = lab.get();
+  unsigned long long* const d_lab64 = lab64.get();
+  int32_t* const d_way = way.get();
+  PlannerCtl* const d_ctl = ctl.get();
+  VHP_HIP(hipMemsetAsync(d_uni, 0, cells * 8, ctx->stream));
+  VHP_HIP(hipMemsetAsync(d_lab, 0xff, cells * 4, ctx->stream));
   const int32_t w0[2] = {start_x, start_y};
   const PlannerCtl c0{1, 0, 0, 0};
   const uint32_t zero = 0;
-  VHP_V(hipMemcpyAsync(d_way, w0, sizeof(w0), hipMemcpyHostToDevice, ctx->stream));
-  VHP_V(hipMemcpyAsync(d_ctl, &c0, sizeof(c0), hipMemcpyHostToDevice, ctx->stream));
-  VHP_V(hipMemcpyAsync(d_lab + ((size_t)start_y * nx + start_x), &zero, 4, hipMemcpyHostToDevice, ctx->stream));  // lightSource_enum(start) = 1
+  VHP_HIP(hipMemcpyAsync(d_way, w0, sizeof(w0), hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(hipMemcpyAsync(d_ctl, &c0, sizeof(c0), hipMemcpyHostToDevice, ctx->stream));
+  VHP_HIP(hipMemcpyAsync(d_lab + ((size_t)start_y * nx + start_x), &zero, 4, hipMemcpyHostToDevice, ctx->stream));  // lightSource_enum(start) = 1
   const unsigned eb = (unsigned)((cells + 255) / 256);
   PlannerCtl h{};
   for (;;) {
     // sweep from the current waypoint (d_way[2*iter]), union + labels, stop test
     int rc = variant_launch_sweep(ctx, d_way + 2 * h.iter, 1, alpha, 1.0, d_loc);
-    if (rc != VHP_OK) { cleanup(); return rc; }
+    if (rc != VHP_OK) return rc;
     hipLaunchKernelGGL(vhp_variant_update, dim3(eb), dim3(256), 0, ctx->stream, d_loc, d_uni, d_lab, cells, threshold, d_ctl);
     hipLaunchKernelGGL(vhp_variant_check, dim3(1), dim3(64), 0, ctx->stream, d_loc, nx, end_x, end_y, threshold, d_ctl);
     hipLaunchKernelGGL(vhp_variant_pick, dim3(1), dim3(1024), 0, ctx->stream, d_uni, nx, ny, end_x, end_y, threshold,
                        (unsigned long long)max_iter, d_way, d_ctl);
-    VHP_V(hipGetLastError());
-    VHP_V(hipMemcpyAsync(&h, d_ctl, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    VHP_V(hipStreamSynchronize(ctx->stream));
+    VHP_HIP(hipGetLastError());
+    VHP_HIP(hipMemcpyAsync(&h, d_ctl, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
     if (h.done) break;
   }
   if (n_waypoints) *n_waypoints = (uint32_t)h.n_way;
-  if (waypoints_xy) VHP_V(hipMemcpyAsync(waypoints_xy, d_way, 2 * (size_t)h.n_way * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (waypoints_xy) VHP_HIP(hipMemcpyAsync(waypoints_xy, d_way, 2 * (size_t)h.n_way * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   if (label) {
     hipLaunchKernelGGL(vhp_variant_labels_to_u64, dim3(eb), dim3(256), 0, ctx->stream, d_lab, d_lab64, cells, ~0ull);
-    VHP_V(hipMemcpyAsync(label, d_lab64, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipMemcpyAsync(label, d_lab64, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
-  if (map_builder) VHP_V(hipMemcpyAsync(map_builder, d_uni, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (local) VHP_V(hipMemcpyAsync(local, d_loc, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-  VHP_V(hipStreamSynchronize(ctx->stream));
-#undef VHP_V
-  cleanup();
+  if (map_builder) VHP_HIP(hipMemcpyAsync(map_builder, d_uni, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (local) VHP_HIP(hipMemcpyAsync(local, d_loc, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
   if (h.status == VHP_ERR_MAX_ITER) ctx->err = "variant planner: max_iter reached";
   if (h.status == VHP_ERR_NOTHING_LIT) ctx->err = "variant planner: no candidate above the threshold";
   return h.status;
@@ -1154,15 +1120,15 @@ int vhp_probe_stores(vhp_ctx* ctx, void* d_buf, unsigned long long bytes, float*
   const int n_tasks = (int)std::min<unsigned long long>(blocks, 2048) * 7;
   // (the task counter lives with the context: vhp_alloc_output probes up to 64 buffers, and a hipFree per probe synchronises the device;
   // the timing pair is the context's own ev0 / ev1 -- nothing here can leak on an early return)
-  if (!ctx->d_probe_counter) VHP_HIP(hipMalloc(&ctx->d_probe_counter, 8));
+  VHP_HIP(ctx->d_probe_counter.grow(8));
   float res[2] = {0.f, 0.f};
   for (int split = 0; split < 2; ++split) {
     float best = 1e30f;
     for (int rep = 0; rep < 4; ++rep) {
-      VHP_HIP(hipMemsetAsync(ctx->d_probe_counter, 0, 4, ctx->stream));
+      VHP_HIP(hipMemsetAsync(ctx->d_probe_counter.get(), 0, 4, ctx->stream));
       VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
       // three workgroups of four wavefronts per CU (52 KB of LDS each keeps a fourth out): what a launch of the pool sweep holds
-      hipLaunchKernelGGL(vhp_store_probe_kernel, dim3((unsigned)ctx->n_cus * 3), dim3(256), 52 * 1024, ctx->stream, static_cast<char*>(d_buf), n_tasks, split, ctx->d_probe_counter);
+      hipLaunchKernelGGL(vhp_store_probe_kernel, dim3((unsigned)ctx->n_cus * 3), dim3(256), 52 * 1024, ctx->stream, static_cast<char*>(d_buf), n_tasks, split, ctx->d_probe_counter.get());
       VHP_HIP(hipGetLastError());
       VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
       VHP_HIP(hipEventSynchronize(ctx->ev1));
@@ -1286,7 +1252,7 @@ int vhp_planner_solve(vhp_ctx* ctx, int start_x, int start_y, int end_x, int end
         l.planner_dev = &d;
         return launch_batch_sweep<double>(ctx, ctx->map, d.pivots, 1, d.vis_local, true, {ctx->opt_field_stride, false}, l);
       };
-    return vhp::planner_solve(ctx->pl, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y, threshold, max_iter,
+    return vhp::planner_solve(ctx->pl, pm, ctx->d_occ.get(), ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y, threshold, max_iter,
                               came_from, vis_global, vis_local, pivots_xy, n_pivots, msg);
   });
 }
@@ -1308,7 +1274,7 @@ int vhp_planner_solve_speculative(vhp_ctx* ctx, int start_x, int start_y, int en
         return launch_batch_sweep<double>(ctx, ctx->map, cand, n, cache, true, {}, l);  // (the cache holds packed fields)
       };
     int st[3] = {0, 0, 0};
-    const int rc = vhp::planner_solve_speculative(ctx->pl, ctx->spec, pm, ctx->d_occ, ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y,
+    const int rc = vhp::planner_solve_speculative(ctx->pl, ctx->spec, pm, ctx->d_occ.get(), ctx->stream, ctx->ev0, ctx->ev1, start_x, start_y, end_x, end_y,
                                                   threshold, max_iter, k, mode, came_from, vis_global, vis_local, pivots_xy, n_pivots, st, msg);
     if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2]; }
     return rc;
@@ -1323,11 +1289,11 @@ int vhp_planner_solve_device(vhp_ctx* ctx, int start_x, int start_y, int end_x, 
 int vhp_planner_results_device(vhp_ctx* ctx, const uint32_t** labels, const double** vis_global, const double** vis_local,
                                const int32_t** pivots_xy) {
   if (!ctx) return VHP_ERR_ARG;
-  if (!ctx->pl.vis_global) return fail(ctx, VHP_ERR_ARG, "vhp_planner_results_device: no planner solve has run on this map");
-  if (labels) *labels = ctx->pl.label;
-  if (vis_global) *vis_global = ctx->pl.vis_global;
-  if (vis_local) *vis_local = ctx->pl.vis_local_out ? ctx->pl.vis_local_out : ctx->pl.vis_local;
-  if (pivots_xy) *pivots_xy = ctx->pl.pivots;
+  if (!ctx->pl.vis_global.get()) return fail(ctx, VHP_ERR_ARG, "vhp_planner_results_device: no planner solve has run on this map");
+  if (labels) *labels = ctx->pl.label.get();
+  if (vis_global) *vis_global = ctx->pl.vis_global.get();
+  if (vis_local) *vis_local = ctx->pl.vis_local_out ? ctx->pl.vis_local_out : ctx->pl.vis_local.get();
+  if (pivots_xy) *pivots_xy = ctx->pl.pivots.get();
   return VHP_OK;
 }
 
@@ -1340,7 +1306,7 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
   if (!queries || (maps && !map_idx) || !thresholds || !status || !n_pivots) return fail(ctx, VHP_ERR_ARG, who + ": null array");
   if (max_iter > (1u << 24)) return fail(ctx, VHP_ERR_ARG, "max_iter too large");
   const auto [b, m, none_solved] = batch_on(ctx, maps);
-  if (!m.rows) return fail(ctx, VHP_ERR_NO_MAP, who + (maps ? ": no maps set" : ": no map set"));
+  if (!m.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, who + (maps ? ": no maps set" : ": no map set"));
   for (int q = 0; maps && q < n_queries; ++q)
     if (map_idx[q] < 0 || map_idx[q] >= m.n) return fail(ctx, VHP_ERR_ARG, who + ": query " + std::to_string(q) + ": map index outside the stack");
   VHP_ON_DEVICE(ctx);
@@ -1349,12 +1315,11 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
   b.lat_sweep = nullptr;
   b.front_sweep = nullptr;
   if (G > 0) {
-    if (maps && !m.dmap) {  // (the stack's diagonal maps: built once, by the first batch that sweeps them)
-      VHP_HIP(hipMalloc(&m.dmap, vhp::lat_diag_map_bytes(m.nx, m.ny) * m.n));
-      const hipError_t e = vhp::lat_pack_diag_stack(m.rows, m.n, m.nx, m.ny, m.wpr, m.dmap, ctx->stream);
+    if (maps && !m.dmap.get()) {  // (the stack's diagonal maps: built once, by the first batch that sweeps them)
+      VHP_HIP(m.dmap.grow(vhp::lat_diag_map_bytes(m.nx, m.ny) * m.n));
+      const hipError_t e = vhp::lat_pack_diag_stack(m.rows.get(), m.n, m.nx, m.ny, m.wpr, m.dmap.get(), ctx->stream);
       if (e != hipSuccess) {
-        (void)hipFree(m.dmap);
-        m.dmap = nullptr;
+        m.dmap.reset();
         return fail(ctx, VHP_ERR_HIP, who + ": diagonal maps: " + hipGetErrorString(e));
       }
     }
@@ -1362,7 +1327,7 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     vhp::PackedMaps* pk = &m;
     b.lat_sweep = [ctx, bs, pk](const int32_t* cand, const int32_t* d_map_idx, int n, double* out) {
       vhp::LatLaunch l;
-      l.slot_base = reinterpret_cast<const int*>(bs->n_done + 1);  // (a zero: field g of the launch is query g's)
+      l.slot_base = reinterpret_cast<const int*>(bs->n_done.get() + 1);  // (a zero: field g of the launch is query g's)
       l.dark_unwritten = true;
       l.map_idx = d_map_idx;  // (null on the single map)
       return launch_batch_sweep<double>(ctx, *pk, cand, n, out, true, {}, l);  // (the queries' local fields are packed)
@@ -1370,7 +1335,7 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     ctx->last_kernel = 4;
   } else {
     const vhp::SweepPlan plan = plan_for_grid(ctx, m, 1, true);
-    hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, &ctx->d_bnd, &ctx->d_bnd_cap);
+    hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, ctx->d_bnd);
     if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
     // (where the latency sweep does not take a single source: vhp_planner_sweep, as planner_solve launches it)
     b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int k) {
@@ -1384,9 +1349,9 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     };
     ctx->last_kernel = 1;
   }
-  const vhp::BatchStack st{map_idx, m.rows, (long long)m.ny * m.wpr, m.wpr};
+  const vhp::BatchStack st{map_idx, m.rows.get(), (long long)m.ny * m.wpr, m.wpr};
   std::string msg;
-  const int rc = vhp::planner_solve_batch(b, pm, maps ? nullptr : ctx->d_occ, maps || ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream,
+  const int rc = vhp::planner_solve_batch(b, pm, maps ? nullptr : ctx->d_occ.get(), maps || ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream,
                                           ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg,
                                           maps ? &st : nullptr);
   ctx->timed = true;

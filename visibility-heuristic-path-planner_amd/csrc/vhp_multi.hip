@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "vhp.h"
+#include "vhp_devbuf.hip.h"
 
 namespace {
 // the few RCCL entry points used, by their C signatures (rccl.h: ncclResult_t is an enum, 0 = success; ncclComm_t an opaque pointer)
@@ -68,17 +69,15 @@ struct vhp_multi {
   std::vector<int> device;
   std::vector<hipStream_t> stream;
   std::vector<std::vector<hipStream_t>> lane;  // lane[to][k]: the stream of the copy from device (to + k) mod N to device `to`
-  std::vector<int32_t*> d_src;
-  std::vector<size_t> d_src_cap;
+  std::vector<vhp::DevBuf<int32_t>> d_src;  // per device, grow-only (vhp_devbuf.hpp)
   std::vector<hipEvent_t> done;
   int nx = 0, ny = 0;
   std::string err;
   Rccl rccl;
   std::vector<void*> comms;  // one communicator per device when the RCCL path is on
   // vhp_multi_union_fields: every device's N partial unions and their label fields (its own partial in slot d)
-  std::vector<void*> parts_best;
-  std::vector<int32_t*> parts_arg;
-  std::vector<size_t> parts_cap;   // bytes of parts_best[d] (parts_arg[d] holds the matching N * cells int32)
+  std::vector<vhp::DevBuf<char>> parts_best;
+  std::vector<vhp::DevBuf<int32_t>> parts_arg;
 };
 
 namespace {
@@ -157,7 +156,7 @@ int vhp_multi_create(const int* device_ordinals, int n_devices, vhp_multi** out)
     vhp_set_stream(c, s);
     m->ctx.push_back(c); m->device.push_back(device_ordinals[d]); m->stream.push_back(s); m->done.push_back(e);
     m->lane.push_back(lanes);
-    m->d_src.push_back(nullptr); m->d_src_cap.push_back(0);
+    m->d_src.emplace_back();
   }
   // peer access for the gather (a pair that cannot is served through the host by hipMemcpyPeerAsync itself)
   for (int a = 0; a < n_devices; ++a)
@@ -180,9 +179,10 @@ int vhp_multi_destroy(vhp_multi* m) {
     for (void* c : m->comms) if (c) (void)m->rccl.CommDestroy(c);
   for (size_t d = 0; d < m->ctx.size(); ++d) {
     DevGuard g(m->device[d]);
-    if (m->d_src[d]) (void)hipFree(m->d_src[d]);
-    if (d < m->parts_best.size() && m->parts_best[d]) (void)hipFree(m->parts_best[d]);
-    if (d < m->parts_arg.size() && m->parts_arg[d]) (void)hipFree(m->parts_arg[d]);
+    // (freed here, on their device -- not by the destructors behind `delete m`, which run on whatever device is current)
+    m->d_src[d].reset();
+    if (d < m->parts_best.size()) m->parts_best[d].reset();
+    if (d < m->parts_arg.size()) m->parts_arg[d].reset();
     if (m->done[d]) (void)hipEventDestroy(m->done[d]);
     vhp_destroy(m->ctx[d]);
     for (hipStream_t l : m->lane[d]) if (l) (void)hipStreamDestroy(l);
@@ -247,14 +247,9 @@ int vhp_multi_sweep_batch(vhp_multi* m, const int32_t* src_xy, int n_src, int va
     if (hi == lo) continue;
     DevGuard g(m->device[d]);
     const size_t bytes = (size_t)(hi - lo) * 2 * sizeof(int32_t);
-    if (m->d_src_cap[d] < bytes) {
-      if (m->d_src[d]) (void)hipFree(m->d_src[d]);
-      m->d_src[d] = nullptr; m->d_src_cap[d] = 0;
-      if (hipMalloc(&m->d_src[d], bytes) != hipSuccess) { (void)hipGetLastError(); drain(m, d); return mfail(m, VHP_ERR_HIP, "vhp_multi_sweep_batch: out of device memory for the sources"); }
-      m->d_src_cap[d] = bytes;
-    }
-    if (hipMemcpyAsync(m->d_src[d], src_xy + 2 * (size_t)lo, bytes, hipMemcpyHostToDevice, m->stream[d]) != hipSuccess) { drain(m, d + 1); return mfail(m, VHP_ERR_HIP, "source upload failed"); }
-    const int rc = vhp_sweep_batch_device(m->ctx[d], m->d_src[d], hi - lo, variant, dtype, d_out_per_device[d]);
+    if (m->d_src[d].grow(bytes) != hipSuccess) { (void)hipGetLastError(); drain(m, d); return mfail(m, VHP_ERR_HIP, "vhp_multi_sweep_batch: out of device memory for the sources"); }
+    if (hipMemcpyAsync(m->d_src[d].get(), src_xy + 2 * (size_t)lo, bytes, hipMemcpyHostToDevice, m->stream[d]) != hipSuccess) { drain(m, d + 1); return mfail(m, VHP_ERR_HIP, "source upload failed"); }
+    const int rc = vhp_sweep_batch_device(m->ctx[d], m->d_src[d].get(), hi - lo, variant, dtype, d_out_per_device[d]);
     if (rc != VHP_OK) { drain(m, d + 1); return mfail(m, rc, std::string("device ") + std::to_string(m->device[d]) + ": " + vhp_last_error(m->ctx[d])); }
   }
   int worst = VHP_OK;
@@ -327,27 +322,20 @@ int vhp_multi_union_fields(vhp_multi* m, int n_src, int dtype, void* const* d_sh
     vhp_multi_shard_bounds(n_src, nd, d, &lo, &hi);
     if ((hi > lo && !d_shard_per_device[d]) || !d_best_per_device[d] || !d_arg_per_device[d]) return mfail(m, VHP_ERR_ARG, "vhp_multi_union_fields: missing buffer");
   }
-  m->parts_best.resize((size_t)nd, nullptr);
-  m->parts_arg.resize((size_t)nd, nullptr);
-  m->parts_cap.resize((size_t)nd, 0);
+  m->parts_best.resize((size_t)nd);
+  m->parts_arg.resize((size_t)nd);
   // 1. every device reduces its own shard into slot d of its table of partials (an empty shard: the neutral partial)
   for (int d = 0; d < nd; ++d) {
     DevGuard g(m->device[d]);
-    if (m->parts_cap[d] < (size_t)nd * cells * el) {
-      if (m->parts_best[d]) (void)hipFree(m->parts_best[d]);
-      if (m->parts_arg[d]) (void)hipFree(m->parts_arg[d]);
-      m->parts_best[d] = nullptr; m->parts_arg[d] = nullptr; m->parts_cap[d] = 0;
-      if (hipMalloc(&m->parts_best[d], (size_t)nd * cells * el) != hipSuccess || hipMalloc(&m->parts_arg[d], (size_t)nd * cells * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        drain(m, d);
-        return mfail(m, VHP_ERR_HIP, "vhp_multi_union_fields: out of device memory for the partial unions");
-      }
-      m->parts_cap[d] = (size_t)nd * cells * el;
+    if (m->parts_best[d].grow((size_t)nd * cells * el) != hipSuccess || m->parts_arg[d].grow((size_t)nd * cells * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      drain(m, d);
+      return mfail(m, VHP_ERR_HIP, "vhp_multi_union_fields: out of device memory for the partial unions");
     }
     int lo, hi;
     vhp_multi_shard_bounds(n_src, nd, d, &lo, &hi);
-    const int rc = vhp_union_fields_device(m->ctx[d], d_shard_per_device[d], hi - lo, dtype, lo, static_cast<char*>(m->parts_best[d]) + (size_t)d * cells * el,
-                                           m->parts_arg[d] + (size_t)d * cells);
+    const int rc = vhp_union_fields_device(m->ctx[d], d_shard_per_device[d], hi - lo, dtype, lo, m->parts_best[d].get() + (size_t)d * cells * el,
+                                           m->parts_arg[d].get() + (size_t)d * cells);
     if (rc != VHP_OK) { drain(m, d + 1); return mfail(m, rc, std::string("device ") + std::to_string(m->device[d]) + ": " + vhp_last_error(m->ctx[d])); }
   }
   for (int d = 0; d < nd; ++d) {
@@ -359,9 +347,9 @@ int vhp_multi_union_fields(vhp_multi* m, int n_src, int dtype, void* const* d_sh
     int rc = m->rccl.GroupStart();
     for (int d = 0; rc == 0 && d < nd; ++d) {
       DevGuard g(m->device[d]);
-      rc = m->rccl.AllGather(static_cast<char*>(m->parts_best[d]) + (size_t)d * cells * el, m->parts_best[d], cells, dtype == VHP_F64 ? kNcclFloat64 : kNcclFloat32,
+      rc = m->rccl.AllGather(m->parts_best[d].get() + (size_t)d * cells * el, m->parts_best[d].get(), cells, dtype == VHP_F64 ? kNcclFloat64 : kNcclFloat32,
                              m->comms[d], m->stream[d]);
-      if (rc == 0) rc = m->rccl.AllGather(m->parts_arg[d] + (size_t)d * cells, m->parts_arg[d], cells, kNcclInt32, m->comms[d], m->stream[d]);
+      if (rc == 0) rc = m->rccl.AllGather(m->parts_arg[d].get() + (size_t)d * cells, m->parts_arg[d].get(), cells, kNcclInt32, m->comms[d], m->stream[d]);
     }
     const int rc_end = m->rccl.GroupEnd();
     if (rc == 0) rc = rc_end;
@@ -372,10 +360,10 @@ int vhp_multi_union_fields(vhp_multi* m, int n_src, int dtype, void* const* d_sh
       for (int to = 0; to < nd; ++to) {
         const int from = (to + k) % nd;
         DevGuard g(m->device[to]);
-        hipError_t e = hipMemcpyPeerAsync(static_cast<char*>(m->parts_best[to]) + (size_t)from * cells * el, m->device[to],
-                                          static_cast<char*>(m->parts_best[from]) + (size_t)from * cells * el, m->device[from], cells * el, m->lane[to][k]);
+        hipError_t e = hipMemcpyPeerAsync(m->parts_best[to].get() + (size_t)from * cells * el, m->device[to],
+                                          m->parts_best[from].get() + (size_t)from * cells * el, m->device[from], cells * el, m->lane[to][k]);
         if (e == hipSuccess)
-          e = hipMemcpyPeerAsync(m->parts_arg[to] + (size_t)from * cells, m->device[to], m->parts_arg[from] + (size_t)from * cells, m->device[from], cells * 4, m->lane[to][k]);
+          e = hipMemcpyPeerAsync(m->parts_arg[to].get() + (size_t)from * cells, m->device[to], m->parts_arg[from].get() + (size_t)from * cells, m->device[from], cells * 4, m->lane[to][k]);
         if (e != hipSuccess) { drain(m, nd); return mfail(m, VHP_ERR_HIP, std::string("peer copy of a partial union: ") + hipGetErrorString(e)); }
       }
     for (int d = 0; d < nd; ++d) {
@@ -386,7 +374,7 @@ int vhp_multi_union_fields(vhp_multi* m, int n_src, int dtype, void* const* d_sh
   }
   // 3. every device merges the N partials (a tie goes to the lowest label: the lowest source index)
   for (int d = 0; d < nd; ++d) {
-    const int rc = vhp_union_partials_device(m->ctx[d], m->parts_best[d], m->parts_arg[d], nd, dtype, d_best_per_device[d], d_arg_per_device[d]);
+    const int rc = vhp_union_partials_device(m->ctx[d], m->parts_best[d].get(), m->parts_arg[d].get(), nd, dtype, d_best_per_device[d], d_arg_per_device[d]);
     if (rc != VHP_OK) { drain(m, d + 1); return mfail(m, rc, std::string("device ") + std::to_string(m->device[d]) + ": " + vhp_last_error(m->ctx[d])); }
   }
   int worst = VHP_OK;

@@ -79,17 +79,9 @@ __global__ void __launch_bounds__(64) vhp_paths_walk(PathsDev p) {
 // The context's scratch of the path calls: the parent tables and walk buffers, and the host forms' staging.  Grow-only; sized by pivots
 // and queries, not by the grid, so it outlives the maps (freed with the context).
 struct PathsScratch {
-  uint32_t* d = nullptr;
-  size_t cap = 0;       // bytes
-  char* out = nullptr;
-  size_t out_cap = 0;
+  DevBuf<uint32_t> d;
+  DevBuf<char> out;
 };
-
-inline void paths_free(PathsScratch& s) {
-  if (s.d) (void)hipFree(s.d);
-  if (s.out) (void)hipFree(s.out);
-  s = PathsScratch{};
-}
 
 // Launches the two kernels for p (slot, nb, the solve's arrays, the output pointers filled in by the caller) on stream.
 inline hipError_t paths_launch(PathsScratch& s, PathsDev p, hipStream_t stream) {
@@ -98,14 +90,8 @@ inline hipError_t paths_launch(PathsScratch& s, PathsDev p, hipStream_t stream) 
   for (int q = 0; q < p.n_queries; ++q)
     if (p.slot[q] >= 0) { p.max_nb = std::max(p.max_nb, p.nb[q]); any = true; }
   const size_t bytes = (size_t)p.n_queries * paths_scratch_words(p.max_nb) * sizeof(uint32_t);
-  if (s.cap < bytes) {
-    if (s.d) (void)hipFree(s.d);   // (waits for whatever still reads it)
-    s.d = nullptr;
-    s.cap = 0;
-    if (hipError_t e = hipMalloc(&s.d, bytes); e != hipSuccess) return e;
-    s.cap = bytes;
-  }
-  p.scratch = s.d;
+  if (hipError_t e = s.d.grow(bytes); e != hipSuccess) return e;   // (a free waits for whatever still reads the memory)
+  p.scratch = s.d.get();
   if (any) {
     hipLaunchKernelGGL(vhp_paths_parents, dim3((p.max_nb + 1 + 255) / 256, p.n_queries), dim3(256), 0, stream, p);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -114,45 +100,63 @@ inline hipError_t paths_launch(PathsScratch& s, PathsDev p, hipStream_t stream) 
   return hipGetLastError();
 }
 
-// The host form: the same launches into staging, ONE copy of at most n_queries * (8 * cap + 16) bytes, one synchronisation; only the
-// points of a query whose status is VHP_OK reach the caller's path_xy.
+// The staging of the host forms of the path and the goal calls (vhp_tree.hip.h), n rows of results -- a row per query or per goal -- in
+// one piece of device memory: every row's length (8 bytes), status (4) and n_path (4), then scap points of 8 bytes per row.
+struct PathStaging {
+  size_t n;
+  bool points;     // the caller takes the points (path_xy)
+  uint32_t scap;
+  size_t head() const { return 16 * n; }
+  size_t bytes() const { return head() + 8 * (size_t)scap * n; }
+
+  // For the paths of p's solve, `cap` points per row asked for (none without path_xy).
+  // (no path has more than max_nb + 3 points: room beyond that would only be copied; a path of more than `cap` points still exceeds the
+  // staging's room, as scap < cap only where no path reaches scap)
+  PathStaging(const PathsDev& p, size_t rows, const int32_t* path_xy, uint32_t cap) : n(rows), points(path_xy != nullptr) {
+    uint32_t max_nb = 0;
+    for (int q = 0; q < p.n_queries; ++q)
+      if (p.slot[q] >= 0) max_nb = std::max(max_nb, p.nb[q]);
+    scap = points ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)max_nb + 3) : 0;
+  }
+
+  // Points the outputs of a launch (PathsDev, TreeGoalArgs) into staging at d.
+  template <typename Args>
+  void attach(Args& a, char* d) const {
+    a.length = reinterpret_cast<double*>(d);
+    a.status = reinterpret_cast<int32_t*>(d + 8 * n);
+    a.n_path = reinterpret_cast<uint32_t*>(d + 12 * n);
+    a.path_xy = points ? reinterpret_cast<int32_t*>(d + head()) : nullptr;
+    a.cap = scap;
+  }
+
+  // ONE copy of at most n * (8 * cap + 16) bytes back from d, one synchronisation; only the points of a row whose status is VHP_OK
+  // reach the caller's path_xy (`cap` points apart).
+  hipError_t copy_out(const char* d, hipStream_t stream, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length, int32_t* status) const {
+    std::vector<char> h(bytes());
+    if (hipError_t e = hipMemcpyAsync(h.data(), d, h.size(), hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
+    if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
+    const double* hl = reinterpret_cast<const double*>(h.data());
+    const int32_t* hs = reinterpret_cast<const int32_t*>(h.data() + 8 * n);
+    const uint32_t* hn = reinterpret_cast<const uint32_t*>(h.data() + 12 * n);
+    const int32_t* hp = reinterpret_cast<const int32_t*>(h.data() + head());
+    for (size_t r = 0; r < n; ++r) {
+      if (length) length[r] = hl[r];
+      if (status) status[r] = hs[r];
+      if (n_path) n_path[r] = hn[r];
+      if (path_xy && hs[r] == VHP_OK) std::copy(hp + 2 * r * scap, hp + 2 * r * scap + 2 * (size_t)hn[r], path_xy + 2 * r * (size_t)cap);
+    }
+    return hipSuccess;
+  }
+};
+
+// The host form: the same launches into staging.
 inline hipError_t paths_host(PathsScratch& s, PathsDev p, hipStream_t stream, int32_t* path_xy, uint32_t cap, uint32_t* n_path, double* length,
                              int32_t* status) {
-  const size_t Q = (size_t)p.n_queries;
-  uint32_t max_nb = 0;
-  for (int q = 0; q < p.n_queries; ++q)
-    if (p.slot[q] >= 0) max_nb = std::max(max_nb, p.nb[q]);
-  // (no path has more than max_nb + 3 points: room beyond that would only be copied; a path of more than `cap` points still
-  // exceeds the staging's room, as scap < cap only where no path reaches scap)
-  const uint32_t scap = path_xy ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)max_nb + 3) : 0;
-  const size_t head = 16 * Q, bytes = head + 8 * (size_t)scap * Q;
-  if (s.out_cap < bytes) {
-    if (s.out) (void)hipFree(s.out);
-    s.out = nullptr;
-    s.out_cap = 0;
-    if (hipError_t e = hipMalloc(&s.out, bytes); e != hipSuccess) return e;
-    s.out_cap = bytes;
-  }
-  p.length = reinterpret_cast<double*>(s.out);
-  p.status = reinterpret_cast<int32_t*>(s.out + 8 * Q);
-  p.n_path = reinterpret_cast<uint32_t*>(s.out + 12 * Q);
-  p.path_xy = path_xy ? reinterpret_cast<int32_t*>(s.out + head) : nullptr;
-  p.cap = scap;
+  const PathStaging st(p, (size_t)p.n_queries, path_xy, cap);
+  if (hipError_t e = s.out.grow(st.bytes()); e != hipSuccess) return e;
+  st.attach(p, s.out.get());
   if (hipError_t e = paths_launch(s, p, stream); e != hipSuccess) return e;
-  std::vector<char> h(bytes);
-  if (hipError_t e = hipMemcpyAsync(h.data(), s.out, bytes, hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
-  if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
-  const double* hl = reinterpret_cast<const double*>(h.data());
-  const int32_t* hs = reinterpret_cast<const int32_t*>(h.data() + 8 * Q);
-  const uint32_t* hn = reinterpret_cast<const uint32_t*>(h.data() + 12 * Q);
-  const int32_t* hp = reinterpret_cast<const int32_t*>(h.data() + head);
-  for (size_t q = 0; q < Q; ++q) {
-    if (length) length[q] = hl[q];
-    if (status) status[q] = hs[q];
-    if (n_path) n_path[q] = hn[q];
-    if (path_xy && hs[q] == VHP_OK) std::copy(hp + 2 * q * scap, hp + 2 * q * scap + 2 * (size_t)hn[q], path_xy + 2 * q * (size_t)cap);
-  }
-  return hipSuccess;
+  return st.copy_out(s.out.get(), stream, path_xy, cap, n_path, length, status);
 }
 
 }  // namespace vhp

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "vhp.h"
+#include "vhp_devbuf.hip.h"
 #include "vhp_planner_host.hpp"
 #include "vhp_sweep.hip.h"
 #include "vhp_planner_dev.hip.h"
@@ -79,23 +80,26 @@ __global__ void vhp_labels_to_u64(const uint32_t* __restrict__ lab, unsigned lon
   if (k < n) out[k] = lab[k] == kUnlabelled32 ? VHP_UNLABELLED : (unsigned long long)lab[k];
 }
 
-struct PlannerState {
+// The memory of a PlannerState (planner_free drops all of it at once: a member added here needs no other list).
+struct PlannerMem {
+  DevBuf<double> vis_global;
+  DevBuf<double> vis_local;
+  DevBuf<double> vis_local2;         // the second local field of the plain solve (see PlannerDev::vis_other)
+  DevBuf<uint32_t> label;
+  DevBuf<unsigned long long> came64;
+  DevBuf<int32_t> pivots;            // grow-only
+  DevBuf<PlannerCtl> ctl;
+  DevBuf<PlannerKey> partial;
+  DevBuf<unsigned int> ticket;
+  // the host's polls of the control block: two pinned copies and their events (PlannerState::poll_ev), so that the next batch of
+  // iterations is enqueued before the host waits for the last one's copy (planner_poll)
+  PinnedBuf<PlannerCtl> h_ctl;
+};
+
+struct PlannerState : PlannerMem {
   size_t cells = 0;
-  size_t pivot_cap = 0;
-  double* vis_global = nullptr;
-  double* vis_local = nullptr;
-  double* vis_local2 = nullptr;      // the second local field of the plain solve (see PlannerDev::vis_other)
   bool local_uncached = false;       // the local fields are uncached device memory (PlannerDev::local_uncached)
   double* vis_local_out = nullptr;   // where the last solve left its local field (one of the two)
-  uint32_t* label = nullptr;
-  unsigned long long* came64 = nullptr;
-  int32_t* pivots = nullptr;
-  PlannerCtl* ctl = nullptr;
-  PlannerKey* partial = nullptr;
-  unsigned int* ticket = nullptr;
-  // the host's polls of the control block: two pinned copies and their events, so that the next batch of iterations is enqueued
-  // before the host waits for the last one's copy (planner_poll)
-  PlannerCtl* h_ctl = nullptr;
   hipEvent_t poll_ev[2] = {nullptr, nullptr};
   const uint8_t* h_occ = nullptr;   // the caller's host copy of the map if it has one (vhp_set_map), for the start / end validation
   // what the last solve on this state left for vhp_planner_path: 0 nothing (no solve since the map was set, or one that failed in the
@@ -119,20 +123,10 @@ struct PlannerState {
 };
 
 inline void planner_free(PlannerState& s) {
-  void* dev[] = {s.vis_global, s.vis_local, s.vis_local2, s.label, s.came64, s.pivots, s.ctl, s.partial, s.ticket};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (s.h_ctl) (void)hipHostFree(s.h_ctl);
+  static_cast<PlannerMem&>(s) = PlannerMem{};
   for (auto& e : s.poll_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  s.vis_global = s.vis_local = s.vis_local2 = s.vis_local_out = nullptr;
-  s.label = nullptr;
-  s.came64 = nullptr;
-  s.pivots = nullptr;
-  s.ctl = s.h_ctl = nullptr;
-  s.partial = nullptr;
-  s.ticket = nullptr;
+  s.vis_local_out = nullptr;
   s.cells = 0;
-  s.pivot_cap = 0;
   s.path_state = 0;
 }
 
@@ -181,46 +175,45 @@ inline int planner_validate(const PlannerState& s, const uint8_t* d_occ, int nx,
 // only grows, and the second local field (PlannerDev::vis_other) is allocated once, where a solve asks for it.  What a solve resets
 // is its own business.
 inline int planner_ensure_state(PlannerState& s, size_t cells, size_t pivot_ints, bool second_local, std::string* msg) {
-  auto alloc_local = [&](double** p) -> hipError_t {
-    return s.local_uncached ? hipExtMallocWithFlags(reinterpret_cast<void**>(p), cells * 8, hipDeviceMallocUncached) : hipMalloc(p, cells * 8);
+  auto alloc_local = [&](DevBuf<double>& b) -> hipError_t {   // (b is empty)
+    if (!s.local_uncached) return b.grow(cells * 8);
+    void* p = nullptr;
+    const hipError_t e = hipExtMallocWithFlags(&p, cells * 8, hipDeviceMallocUncached);
+    if (e == hipSuccess) b.adopt(static_cast<double*>(p), cells * 8);   // (freed by hipFree like the rest)
+    return e;
   };
   if (s.cells != cells) {
     planner_free(s);
-    VHP_PL_HIP(hipMalloc(&s.vis_global, cells * 8));
+    VHP_PL_HIP(s.vis_global.grow(cells * 8));
     // (an experiment of the one-kernel iteration: vhp_capi.hip; read where the local fields are allocated, so that the flag the
     // kernels get says what the memory is whichever solve came first)
     s.local_uncached = std::getenv("VHP_PLANNER_UNCACHED") != nullptr;
-    VHP_PL_HIP(alloc_local(&s.vis_local));
-    VHP_PL_HIP(hipMalloc(&s.label, cells * 4));
-    VHP_PL_HIP(hipMalloc(&s.came64, cells * 8));
-    VHP_PL_HIP(hipMalloc(&s.ctl, sizeof(PlannerCtl) + 16));   // (+ the 16-byte pivot record: PlannerDev::rec)
-    VHP_PL_HIP(hipMalloc(&s.partial, kSpecPartials * sizeof(PlannerKey)));
-    VHP_PL_HIP(hipMalloc(&s.ticket, 2 * sizeof(unsigned int)));   // ([1]: the sweep workgroups of a one-kernel iteration that have finished)
+    VHP_PL_HIP(alloc_local(s.vis_local));
+    VHP_PL_HIP(s.label.grow(cells * 4));
+    VHP_PL_HIP(s.came64.grow(cells * 8));
+    VHP_PL_HIP(s.ctl.grow(sizeof(PlannerCtl) + 16));   // (+ the 16-byte pivot record: PlannerDev::rec)
+    VHP_PL_HIP(s.partial.grow(kSpecPartials * sizeof(PlannerKey)));
+    VHP_PL_HIP(s.ticket.grow(2 * sizeof(unsigned int)));   // ([1]: the sweep workgroups of a one-kernel iteration that have finished)
     s.cells = cells;
   }
-  if (s.pivot_cap < pivot_ints) {
-    if (s.pivots) (void)hipFree(s.pivots);
-    s.pivots = nullptr;
-    VHP_PL_HIP(hipMalloc(&s.pivots, pivot_ints * sizeof(int32_t)));
-    s.pivot_cap = pivot_ints;
-  }
-  if (second_local && !s.vis_local2) VHP_PL_HIP(alloc_local(&s.vis_local2));
+  VHP_PL_HIP(s.pivots.grow(pivot_ints * sizeof(int32_t)));
+  if (second_local && !s.vis_local2.get()) VHP_PL_HIP(alloc_local(s.vis_local2));
   return VHP_OK;
 }
 
 // What the kernels of a solve on s get: its arrays, the query's end point and loop condition, one local field.
 inline PlannerDev planner_dev(const PlannerState& s, int nx, int ny, double threshold, int end_x, int end_y, uint64_t max_iter) {
   PlannerDev d;
-  d.vis_global = s.vis_global;
-  d.vis_local = s.vis_local;
+  d.vis_global = s.vis_global.get();
+  d.vis_local = s.vis_local.get();
   d.vis_other = nullptr;
-  d.label = s.label;
-  d.pivots = s.pivots;
-  d.ctl = s.ctl;
-  d.rec = reinterpret_cast<int*>(s.ctl + 1);
+  d.label = s.label.get();
+  d.pivots = s.pivots.get();
+  d.ctl = s.ctl.get();
+  d.rec = reinterpret_cast<int*>(s.ctl.get() + 1);
   d.local_uncached = s.local_uncached ? 1 : 0;
-  d.partial = s.partial;
-  d.ticket = s.ticket;
+  d.partial = s.partial.get();
+  d.ticket = s.ticket.get();
   d.threshold = threshold;
   d.scale = planner_scale(nx, ny);
   d.end_x = end_x;
@@ -267,11 +260,11 @@ inline int planner_poll(hipStream_t stream, const T* dev, T* h, hipEvent_t* ev, 
 // first solve)
 template <typename Enqueue>
 inline int planner_poll_ctl(PlannerState& s, hipStream_t stream, Enqueue enqueue, PlannerCtl* out, std::string* msg) {
-  if (!s.h_ctl) {
-    VHP_PL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_ctl), 2 * sizeof(PlannerCtl)));
+  if (!s.h_ctl.get()) {
+    VHP_PL_HIP(s.h_ctl.grow(2 * sizeof(PlannerCtl)));
     for (auto& e : s.poll_ev) VHP_PL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  return planner_poll(stream, s.ctl, s.h_ctl, s.poll_ev, enqueue, [](const PlannerCtl& c) { return c.done != 0; }, "planner poll", out, msg);
+  return planner_poll(stream, s.ctl.get(), s.h_ctl.get(), s.poll_ev, enqueue, [](const PlannerCtl& c) { return c.done != 0; }, "planner poll", out, msg);
 }
 
 // A sweep kernel of the planner's -- vhp_planner_sweep<R, MULTI> on `quadrants` = 4 workgroups, vhp_spec_sweep<R, MULTI> on 4 K -- in
@@ -321,8 +314,8 @@ inline int planner_finish(PlannerState& s, hipStream_t stream, const PlannerCtl&
   s.last_nb = nb;
   s.last_end_x = end_x;
   s.last_end_y = end_y;
-  return planner_copy_out(stream, s.cells, s.label, s.came64, s.vis_global, s.vis_local_out, s.pivots, nb, came_from, vis_global, vis_local,
-                          pivots_xy, msg);
+  return planner_copy_out(stream, s.cells, s.label.get(), s.came64.get(), s.vis_global.get(), s.vis_local_out, s.pivots.get(), nb, came_from,
+                          vis_global, vis_local, pivots_xy, msg);
 }
 
 inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ, hipStream_t stream, hipEvent_t ev0,
@@ -341,12 +334,12 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
   const bool two_fields = (bool)s.lat_sweep;
   if (const int rc = planner_ensure_state(s, cells, pcap, two_fields, msg); rc != VHP_OK) return rc;
   // reset(): visibility_global_ = 0, visibility_ = 0, cameFrom_ = 1e15   (solver.cpp:42-47)
-  VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, cells * 8, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.vis_local, 0, cells * 8, stream));
-  if (s.vis_local2) VHP_PL_HIP(hipMemsetAsync(s.vis_local2, 0, cells * 8, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, cells * 4, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, pcap * sizeof(int32_t), stream));
-  VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, 2 * sizeof(unsigned int), stream));
+  VHP_PL_HIP(hipMemsetAsync(s.vis_global.get(), 0, cells * 8, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.vis_local.get(), 0, cells * 8, stream));
+  if (s.vis_local2.get()) VHP_PL_HIP(hipMemsetAsync(s.vis_local2.get(), 0, cells * 8, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.label.get(), 0xff, cells * 4, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.pivots.get(), 0, pcap * sizeof(int32_t), stream));
+  VHP_PL_HIP(hipMemsetAsync(s.ticket.get(), 0, 2 * sizeof(unsigned int), stream));
 
   PlannerDev d = planner_dev(s, nx, ny, threshold, end_x, end_y, max_iter);
   size_t launches = 0;
@@ -360,15 +353,15 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
     const int rc = planner_poll_ctl(s, stream, [&]() -> int {
       for (int b = 0; b < kPollIterations; ++b, ++launches) {
         if (two_fields) {
-          d.vis_local = (launches & 1) ? s.vis_local2 : s.vis_local;
-          d.vis_other = (launches & 1) ? s.vis_local : s.vis_local2;
+          d.vis_local = (launches & 1) ? s.vis_local2.get() : s.vis_local.get();
+          d.vis_other = (launches & 1) ? s.vis_local.get() : s.vis_local2.get();
         }
         if (s.lat_iteration) {
           const hipError_t ei = s.lat_iteration(d);
           if (ei != hipSuccess) { *msg = std::string("planner launch: ") + hipGetErrorString(ei); return VHP_ERR_HIP; }
           continue;
         }
-        hipError_t e = s.lat_sweep ? s.lat_sweep(d.pivots, &s.ctl->nb, &s.ctl->done, d.rec, d.vis_local, true)
+        hipError_t e = s.lat_sweep ? s.lat_sweep(d.pivots, &d.ctl->nb, &d.ctl->done, d.rec, d.vis_local, true)
                                    : with_sweep_shape(R, multi, [&](auto r, auto mr) {
                                        return launch_planner_kernel<r(), mr()>(vhp_planner_sweep<r(), mr()>, 4, W, s.raise_lds, stream, m, d);
                                      });
@@ -383,7 +376,7 @@ inline int planner_solve(PlannerState& s, const DevMap& m, const uint8_t* d_occ,
   VHP_PL_HIP(hipEventRecord(ev1, stream));
 
   // (launch number n is iteration number n while the loop runs; the last iteration that ran is number iters - 1)
-  s.vis_local_out = (two_fields && ctl.iters > 0 && ((ctl.iters - 1) & 1)) ? s.vis_local2 : s.vis_local;
+  s.vis_local_out = (two_fields && ctl.iters > 0 && ((ctl.iters - 1) & 1)) ? s.vis_local2.get() : s.vis_local.get();
   if (const int rc = planner_finish(s, stream, ctl, end_x, end_y, came_from, vis_global, vis_local, pivots_xy, n_pivots, msg); rc != VHP_OK) return rc;
   if (const char* why = planner_status_message(ctl.status)) *msg = why;
   return ctl.status;
@@ -788,16 +781,9 @@ __global__ void vhp_spec_export_local(DevMap m, PlannerDev d, SpecDev sp) {
 
 struct SpecState {
   size_t cells = 0;
-  double* cache = nullptr;
-  SpecCtl* sc = nullptr;
+  DevBuf<double> cache;
+  DevBuf<SpecCtl> sc;
 };
-inline void spec_free(SpecState& s) {
-  if (s.cache) (void)hipFree(s.cache);
-  if (s.sc) (void)hipFree(s.sc);
-  s.cache = nullptr;
-  s.sc = nullptr;
-  s.cells = 0;
-}
 
 // The loop of planner_solve with the speculative sweep launches.  stats (3 ints, may be null): iterations whose pivot was
 // cached, iterations that swept, fields swept.  Validates start / end itself, like planner_solve; the caller has sized the round
@@ -813,23 +799,23 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
   const size_t cells = (size_t)nx * ny;
   if (const int rc = planner_ensure_state(s, cells, planner_pivot_ints(max_iter, kSpecMaxK), false, msg); rc != VHP_OK) return rc;
   if (ss.cells != cells) {
-    spec_free(ss);
-    VHP_PL_HIP(hipMalloc(&ss.cache, (size_t)kSpecSlots * cells * 8));
-    VHP_PL_HIP(hipMalloc(&ss.sc, sizeof(SpecCtl)));
+    ss = SpecState{};
+    VHP_PL_HIP(ss.cache.grow((size_t)kSpecSlots * cells * 8));
+    VHP_PL_HIP(ss.sc.grow(sizeof(SpecCtl)));
     ss.cells = cells;
   }
   // (not vis_local: vhp_spec_export_local writes all of it)
-  VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, cells * 8, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, cells * 4, stream));
-  VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, s.pivot_cap * sizeof(int32_t), stream));
-  VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, 2 * sizeof(unsigned int), stream));
-  if (mode == 1) VHP_PL_HIP(hipMemsetAsync(ss.cache, 0, (size_t)2 * K * cells * 8, stream));  // (the two groups of k slots that take turns: vhp_spec_epilogue)
+  VHP_PL_HIP(hipMemsetAsync(s.vis_global.get(), 0, cells * 8, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.label.get(), 0xff, cells * 4, stream));
+  VHP_PL_HIP(hipMemsetAsync(s.pivots.get(), 0, s.pivots.bytes(), stream));
+  VHP_PL_HIP(hipMemsetAsync(s.ticket.get(), 0, 2 * sizeof(unsigned int), stream));
+  if (mode == 1) VHP_PL_HIP(hipMemsetAsync(ss.cache.get(), 0, (size_t)2 * K * cells * 8, stream));  // (the two groups of k slots that take turns: vhp_spec_epilogue)
 
   const PlannerDev d = planner_dev(s, nx, ny, threshold, end_x, end_y, max_iter);
-  s.vis_local_out = s.vis_local;
+  s.vis_local_out = s.vis_local.get();
   SpecDev sp;
-  sp.sc = ss.sc;
-  sp.cache = ss.cache;
+  sp.sc = ss.sc.get();
+  sp.cache = ss.cache.get();
   sp.cells = cells;
   sp.K = K;
   sp.mode = mode;
@@ -844,7 +830,7 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
   {
     const int rc = planner_poll_ctl(s, stream, [&]() -> int {
       for (int b = 0; b < kPollIterations; ++b) {
-        hipError_t e = s.lat_sweep_k ? s.lat_sweep_k(ss.sc->cand, K, &ss.sc->cur_slot, &ss.sc->sweep, &s.ctl->done, ss.cache, mode == 1)
+        hipError_t e = s.lat_sweep_k ? s.lat_sweep_k(sp.sc->cand, K, &sp.sc->cur_slot, &sp.sc->sweep, &d.ctl->done, sp.cache, mode == 1)
                                      : with_sweep_shape(R, multi, [&](auto r, auto mr) {
                                          return launch_planner_kernel<r(), mr()>(vhp_spec_sweep<r(), mr()>, 4 * K, W, s.raise_lds, stream, m, d, sp);
                                        });
@@ -862,7 +848,7 @@ inline int planner_solve_speculative(PlannerState& s, SpecState& ss, const DevMa
   VHP_PL_HIP(hipGetLastError());
   VHP_PL_HIP(hipEventRecord(ev1, stream));
   SpecCtl hc{};
-  VHP_PL_HIP(hipMemcpyAsync(&hc, ss.sc, sizeof(hc), hipMemcpyDeviceToHost, stream));
+  VHP_PL_HIP(hipMemcpyAsync(&hc, sp.sc, sizeof(hc), hipMemcpyDeviceToHost, stream));
 
   if (const int rc = planner_finish(s, stream, ctl, end_x, end_y, came_from, vis_global, vis_local, pivots_xy, n_pivots, msg); rc != VHP_OK) return rc;
   if (stats) { stats[0] = hc.hits; stats[1] = hc.misses; stats[2] = hc.fields_swept; }

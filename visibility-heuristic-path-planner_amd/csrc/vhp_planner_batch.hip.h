@@ -146,24 +146,28 @@ struct BatchStack {
   int wpr;
 };
 
+// The memory of a BatchState (batch_free drops all of it at once: a member added here needs no other list).
+struct BatchMem {
+  DevBuf<double> vis_global;
+  DevBuf<double> local[2];
+  DevBuf<uint32_t> label;
+  DevBuf<int32_t> pivots;
+  DevBuf<BatchCtl> ctl;
+  DevBuf<PlannerKey> partial;
+  DevBuf<unsigned int> ticket;
+  DevBuf<BatchQuery> query;
+  DevBuf<int32_t> cand;
+  DevBuf<int32_t> map_idx;               // per slot: its query's map (a batch on a stack of maps)
+  DevBuf<int4> probe;                    // a batch on a stack: the 2 * kBatchMaxQueries cells of its validation, then their bits (bytes)
+  DevBuf<unsigned int> n_done;           // [0]: done queries of the running group; [1]: zero (the sweep's LatArgs::slot_base)
+  DevBuf<unsigned long long> came64;     // cells: the labels widened for vhp_planner_batch_results
+  PinnedBuf<unsigned int> h_done;        // two copies of the done word (the host's polls)
+};
+
 // The device state of a batch: every array holds one slot per query that passed validation (results stay until the next batch or
 // vhp_set_map), plus the host's view of the last batch.
-struct BatchState {
+struct BatchState : BatchMem {
   size_t cells = 0, slots = 0, pivot_stride = 0;   // what the arrays hold
-  double* vis_global = nullptr;
-  double* local[2] = {nullptr, nullptr};
-  uint32_t* label = nullptr;
-  int32_t* pivots = nullptr;
-  BatchCtl* ctl = nullptr;
-  PlannerKey* partial = nullptr;
-  unsigned int* ticket = nullptr;
-  BatchQuery* query = nullptr;
-  int32_t* cand = nullptr;
-  int32_t* map_idx = nullptr;            // per slot: its query's map (a batch on a stack of maps)
-  int4* probe = nullptr;                 // a batch on a stack: the 2 * kBatchMaxQueries cells of its validation, then their bits (bytes)
-  unsigned int* n_done = nullptr;        // [0]: done queries of the running group; [1]: zero (the sweep's LatArgs::slot_base)
-  unsigned long long* came64 = nullptr;  // cells: the labels widened for vhp_planner_batch_results
-  unsigned int* h_done = nullptr;        // pinned: two copies of the done word (the host's polls)
   hipEvent_t poll_ev[2] = {nullptr, nullptr};
   // the last batch: per query its slot (-1: failed validation), its control block as the loop left it
   bool solved = false;
@@ -180,22 +184,8 @@ struct BatchState {
 };
 
 inline void batch_free(BatchState& s) {
-  void* dev[] = {s.vis_global, s.local[0], s.local[1], s.label, s.pivots, s.ctl, s.partial, s.ticket, s.query, s.cand, s.map_idx, s.probe,
-                 s.n_done, s.came64};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (s.h_done) (void)hipHostFree(s.h_done);
+  static_cast<BatchMem&>(s) = BatchMem{};
   for (auto& e : s.poll_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  s.vis_global = s.local[0] = s.local[1] = nullptr;
-  s.label = nullptr;
-  s.pivots = nullptr;
-  s.ctl = nullptr;
-  s.partial = nullptr;
-  s.ticket = s.n_done = s.h_done = nullptr;
-  s.query = nullptr;
-  s.cand = s.map_idx = nullptr;
-  s.probe = nullptr;
-  s.came64 = nullptr;
   s.cells = s.slots = s.pivot_stride = 0;
   s.solved = false;   // (what the last batch left is gone with it)
 }
@@ -239,11 +229,11 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     }
     if (!pts.empty()) {
       const int n = (int)pts.size();   // (<= 2 * kBatchMaxQueries)
-      if (!s.probe) VHP_PL_HIP(hipMalloc(&s.probe, 2 * kBatchMaxQueries * (sizeof(int4) + 1)));
-      uint8_t* d_bits = reinterpret_cast<uint8_t*>(s.probe + 2 * kBatchMaxQueries);
+      VHP_PL_HIP(s.probe.grow(2 * kBatchMaxQueries * (sizeof(int4) + 1)));
+      uint8_t* d_bits = reinterpret_cast<uint8_t*>(s.probe.get() + 2 * kBatchMaxQueries);
       std::vector<uint8_t> bits(n);
-      VHP_PL_HIP(hipMemcpyAsync(s.probe, pts.data(), n * sizeof(int4), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(vhp_planner_batch_occupancy, dim3(1), dim3(2 * kBatchMaxQueries), 0, stream, s.probe, n, stack->rows,
+      VHP_PL_HIP(hipMemcpyAsync(s.probe.get(), pts.data(), n * sizeof(int4), hipMemcpyHostToDevice, stream));
+      hipLaunchKernelGGL(vhp_planner_batch_occupancy, dim3(1), dim3(2 * kBatchMaxQueries), 0, stream, s.probe.get(), n, stack->rows,
                          stack->rows_stride, stack->wpr, d_bits);
       VHP_PL_HIP(hipGetLastError());
       VHP_PL_HIP(hipMemcpyAsync(bits.data(), d_bits, n, hipMemcpyDeviceToHost, stream));
@@ -275,24 +265,24 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   const bool two_fields = (bool)s.lat_sweep;
   if (!s.lat_sweep) group = 1;
   // (re)allocation: grow-only in queries and pivots; a new grid starts afresh
-  if (s.cells != cells || s.slots < n_run || s.pivot_stride < pstride || (two_fields && !s.local[1] && s.slots)) {
+  if (s.cells != cells || s.slots < n_run || s.pivot_stride < pstride || (two_fields && !s.local[1].get() && s.slots)) {
     const size_t slots = std::max(n_run, s.cells == cells ? s.slots : (size_t)0);
     batch_free(s);
     if (slots > 0) {
-      VHP_PL_HIP(hipMalloc(&s.vis_global, slots * cells * 8));
-      VHP_PL_HIP(hipMalloc(&s.local[0], slots * cells * 8));
-      if (two_fields) VHP_PL_HIP(hipMalloc(&s.local[1], slots * cells * 8));
-      VHP_PL_HIP(hipMalloc(&s.label, slots * cells * 4));
-      VHP_PL_HIP(hipMalloc(&s.pivots, slots * pstride * sizeof(int32_t)));
-      VHP_PL_HIP(hipMalloc(&s.ctl, slots * sizeof(BatchCtl)));
-      VHP_PL_HIP(hipMalloc(&s.partial, slots * kEpilogueBlocks * sizeof(PlannerKey)));
-      VHP_PL_HIP(hipMalloc(&s.ticket, slots * 2 * sizeof(unsigned int)));
-      VHP_PL_HIP(hipMalloc(&s.query, slots * sizeof(BatchQuery)));
-      VHP_PL_HIP(hipMalloc(&s.cand, slots * 2 * sizeof(int32_t)));
-      VHP_PL_HIP(hipMalloc(&s.map_idx, slots * sizeof(int32_t)));
+      VHP_PL_HIP(s.vis_global.grow(slots * cells * 8));
+      VHP_PL_HIP(s.local[0].grow(slots * cells * 8));
+      if (two_fields) VHP_PL_HIP(s.local[1].grow(slots * cells * 8));
+      VHP_PL_HIP(s.label.grow(slots * cells * 4));
+      VHP_PL_HIP(s.pivots.grow(slots * pstride * sizeof(int32_t)));
+      VHP_PL_HIP(s.ctl.grow(slots * sizeof(BatchCtl)));
+      VHP_PL_HIP(s.partial.grow(slots * kEpilogueBlocks * sizeof(PlannerKey)));
+      VHP_PL_HIP(s.ticket.grow(slots * 2 * sizeof(unsigned int)));
+      VHP_PL_HIP(s.query.grow(slots * sizeof(BatchQuery)));
+      VHP_PL_HIP(s.cand.grow(slots * 2 * sizeof(int32_t)));
+      VHP_PL_HIP(s.map_idx.grow(slots * sizeof(int32_t)));
     }
-    VHP_PL_HIP(hipMalloc(&s.n_done, 2 * sizeof(unsigned int)));
-    VHP_PL_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_done), 2 * sizeof(unsigned int)));
+    VHP_PL_HIP(s.n_done.grow(2 * sizeof(unsigned int)));
+    VHP_PL_HIP(s.h_done.grow(2 * sizeof(unsigned int)));
     for (auto& e : s.poll_ev) VHP_PL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     s.cells = cells;
     s.slots = slots;
@@ -304,29 +294,29 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
   VHP_PL_HIP(hipEventRecord(ev0, stream));
   if (n_run > 0) {
     // reset() for every query (solver.cpp:42-47)
-    VHP_PL_HIP(hipMemsetAsync(s.vis_global, 0, n_run * cells * 8, stream));
-    VHP_PL_HIP(hipMemsetAsync(s.local[0], 0, n_run * cells * 8, stream));
-    if (two_fields) VHP_PL_HIP(hipMemsetAsync(s.local[1], 0, n_run * cells * 8, stream));
-    VHP_PL_HIP(hipMemsetAsync(s.label, 0xff, n_run * cells * 4, stream));
-    VHP_PL_HIP(hipMemsetAsync(s.pivots, 0, n_run * s.pivot_stride * sizeof(int32_t), stream));
-    VHP_PL_HIP(hipMemsetAsync(s.ticket, 0, n_run * 2 * sizeof(unsigned int), stream));
-    VHP_PL_HIP(hipMemcpyAsync(s.query, run.data(), n_run * sizeof(BatchQuery), hipMemcpyHostToDevice, stream));
-    if (stack) VHP_PL_HIP(hipMemcpyAsync(s.map_idx, run_map.data(), n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    VHP_PL_HIP(hipMemsetAsync(s.vis_global.get(), 0, n_run * cells * 8, stream));
+    VHP_PL_HIP(hipMemsetAsync(s.local[0].get(), 0, n_run * cells * 8, stream));
+    if (two_fields) VHP_PL_HIP(hipMemsetAsync(s.local[1].get(), 0, n_run * cells * 8, stream));
+    VHP_PL_HIP(hipMemsetAsync(s.label.get(), 0xff, n_run * cells * 4, stream));
+    VHP_PL_HIP(hipMemsetAsync(s.pivots.get(), 0, n_run * s.pivot_stride * sizeof(int32_t), stream));
+    VHP_PL_HIP(hipMemsetAsync(s.ticket.get(), 0, n_run * 2 * sizeof(unsigned int), stream));
+    VHP_PL_HIP(hipMemcpyAsync(s.query.get(), run.data(), n_run * sizeof(BatchQuery), hipMemcpyHostToDevice, stream));
+    if (stack) VHP_PL_HIP(hipMemcpyAsync(s.map_idx.get(), run_map.data(), n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
-  VHP_PL_HIP(hipMemsetAsync(s.n_done, 0, 2 * sizeof(unsigned int), stream));
+  VHP_PL_HIP(hipMemsetAsync(s.n_done.get(), 0, 2 * sizeof(unsigned int), stream));
 
   PlannerBatchDev all;
-  all.vis_global = s.vis_global;
-  all.local[0] = s.local[0];
-  all.local[1] = two_fields ? s.local[1] : nullptr;
-  all.label = s.label;
-  all.pivots = s.pivots;
-  all.ctl = s.ctl;
-  all.partial = s.partial;
-  all.ticket = s.ticket;
-  all.query = s.query;
-  all.cand = s.cand;
-  all.n_done = s.n_done;
+  all.vis_global = s.vis_global.get();
+  all.local[0] = s.local[0].get();
+  all.local[1] = two_fields ? s.local[1].get() : nullptr;
+  all.label = s.label.get();
+  all.pivots = s.pivots.get();
+  all.ctl = s.ctl.get();
+  all.partial = s.partial.get();
+  all.ticket = s.ticket.get();
+  all.query = s.query.get();
+  all.cand = s.cand.get();
+  all.n_done = s.n_done.get();
   all.cells = cells;
   all.pivot_stride = s.pivot_stride;
   all.scale = planner_scale(nx, ny);
@@ -346,7 +336,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     b.ticket += 2 * g0;
     b.query += g0;
     b.cand += 2 * g0;
-    VHP_PL_HIP(hipMemsetAsync(s.n_done, 0, sizeof(unsigned int), stream));
+    VHP_PL_HIP(hipMemsetAsync(all.n_done, 0, sizeof(unsigned int), stream));
     hipLaunchKernelGGL(vhp_planner_batch_init, dim3(1), dim3(64), 0, stream, b, nx, n);
     VHP_PL_HIP(hipGetLastError());
     const int blocks = batch_epilogue_blocks(n);
@@ -356,7 +346,7 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
         const int parity = (int)(launches & 1);
         hipError_t e = hipSuccess;
         if (s.lat_sweep) {
-          e = s.lat_sweep(b.cand, stack ? s.map_idx + g0 : nullptr, n, b.local[parity]);
+          e = s.lat_sweep(b.cand, stack ? s.map_idx.get() + g0 : nullptr, n, b.local[parity]);
         } else {
           e = s.front_sweep(batch_query_dev(b, 0, 0), run_map[g0]);
         }
@@ -368,12 +358,12 @@ inline int planner_solve_batch(BatchState& s, const DevMap& m, const uint8_t* d_
     };
     // (the group's loop ends when the done word counts all its queries)
     unsigned int n_done = 0;
-    const int rc = planner_poll(stream, s.n_done, s.h_done, s.poll_ev, enqueue, [n](unsigned int done) { return done >= (unsigned)n; },
+    const int rc = planner_poll(stream, all.n_done, s.h_done.get(), s.poll_ev, enqueue, [n](unsigned int done) { return done >= (unsigned)n; },
                                 "batch planner poll", &n_done, msg);
     if (rc != VHP_OK) return rc;
   }
   VHP_PL_HIP(hipEventRecord(ev1, stream));
-  if (n_run > 0) VHP_PL_HIP(hipMemcpyAsync(s.h_ctl.data(), s.ctl, n_run * sizeof(BatchCtl), hipMemcpyDeviceToHost, stream));
+  if (n_run > 0) VHP_PL_HIP(hipMemcpyAsync(s.h_ctl.data(), all.ctl, n_run * sizeof(BatchCtl), hipMemcpyDeviceToHost, stream));
   VHP_PL_HIP(hipStreamSynchronize(stream));
   for (int q = 0; q < n_queries; ++q) {
     if (s.slot_of[q] < 0) continue;
@@ -392,10 +382,10 @@ inline void batch_results_device(const BatchState& s, int k, const uint32_t** la
   const size_t f = (size_t)k * s.cells;
   const int iters = s.h_ctl[k].ctl.iters;
   const int which = (s.two_fields && iters > 0 && ((iters - 1) & 1)) ? 1 : 0;
-  if (labels) *labels = s.label + f;
-  if (vis_global) *vis_global = s.vis_global + f;
-  if (vis_local) *vis_local = s.local[which] + f;
-  if (pivots_xy) *pivots_xy = s.pivots + (size_t)k * s.pivot_stride;
+  if (labels) *labels = s.label.get() + f;
+  if (vis_global) *vis_global = s.vis_global.get() + f;
+  if (vis_local) *vis_local = s.local[which].get() + f;
+  if (pivots_xy) *pivots_xy = s.pivots.get() + (size_t)k * s.pivot_stride;
 }
 
 // Host copies of query slot k's results, laid out as planner_solve's outputs (any may be null).
@@ -405,8 +395,8 @@ inline int batch_results_host(BatchState& s, int k, hipStream_t stream, uint64_t
   const double *vg, *vl;
   const int32_t* piv;
   batch_results_device(s, k, &lab, &vg, &vl, &piv);
-  if (came_from && !s.came64) VHP_PL_HIP(hipMalloc(&s.came64, s.cells * 8));
-  return planner_copy_out(stream, s.cells, lab, s.came64, vg, vl, piv, (uint32_t)s.h_ctl[k].ctl.nb, came_from, vis_global, vis_local, pivots_xy, msg,
+  if (came_from) VHP_PL_HIP(s.came64.grow(s.cells * 8));
+  return planner_copy_out(stream, s.cells, lab, s.came64.get(), vg, vl, piv, (uint32_t)s.h_ctl[k].ctl.nb, came_from, vis_global, vis_local, pivots_xy, msg,
                           true);
 }
 

@@ -110,18 +110,11 @@ __global__ void vhp_fill_f64(double* __restrict__ p, double v, size_t n) {
 }
 
 struct QueueScratch {
-  double* work = nullptr;
-  QCell* queue = nullptr;
-  uint8_t* visited = nullptr;
+  DevBuf<double> work;
+  DevBuf<QCell> queue;
+  DevBuf<uint8_t> visited;
   size_t slice = 0, cells = 0;
 };
-
-inline void queue_scratch_free(QueueScratch& q) {
-  if (q.work) (void)hipFree(q.work);
-  if (q.queue) (void)hipFree(q.queue);
-  if (q.visited) (void)hipFree(q.visited);
-  q = QueueScratch();
-}
 
 inline hipError_t launch_queue_sweep_impl(QueueScratch& qs, const DevMap& m, const uint8_t* d_occ, const int32_t* d_src,
                                           int n_src, int dtype, void* d_out, int* d_err, hipStream_t stream) {
@@ -130,11 +123,11 @@ inline hipError_t launch_queue_sweep_impl(QueueScratch& qs, const DevMap& m, con
   // bound scratch to ~1 GiB: 8 (work) + 8*3 (queue) + 1 (visited) bytes per cell and source
   const size_t slice = std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / (cells * 33 + 64)));
   if (qs.slice < slice || qs.cells != cells) {
-    queue_scratch_free(qs);
+    qs = QueueScratch{};
     hipError_t e;
-    if ((e = hipMalloc(&qs.work, slice * cells * 8)) != hipSuccess) return e;
-    if ((e = hipMalloc(&qs.queue, slice * qcap * sizeof(QCell))) != hipSuccess) return e;
-    if ((e = hipMalloc(&qs.visited, slice * cells)) != hipSuccess) return e;
+    if ((e = qs.work.grow(slice * cells * 8)) != hipSuccess) return e;
+    if ((e = qs.queue.grow(slice * qcap * sizeof(QCell))) != hipSuccess) return e;
+    if ((e = qs.visited.grow(slice * cells)) != hipSuccess) return e;
     qs.slice = slice;
     qs.cells = cells;
   }
@@ -142,15 +135,15 @@ inline hipError_t launch_queue_sweep_impl(QueueScratch& qs, const DevMap& m, con
   for (int s0 = 0; s0 < n_src; s0 += (int)slice) {
     const int n = std::min<int>((int)slice, n_src - s0);
     hipError_t e;
-    if ((e = hipMemsetAsync(qs.work, 0, (size_t)n * cells * 8, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(qs.visited, 0, (size_t)n * cells, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(qs.work.get(), 0, (size_t)n * cells * 8, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(qs.visited.get(), 0, (size_t)n * cells, stream)) != hipSuccess) return e;
     void* o = static_cast<char*>(d_out) + (size_t)s0 * cells * esz;
     if (dtype == VHP_F64)
       hipLaunchKernelGGL(vhp_queue_flood<double>, dim3(n), dim3(256), 0, stream, m.nx, m.ny, d_occ, d_src + 2 * (size_t)s0,
-                         qs.work, qs.queue, qs.visited, static_cast<double*>(o), (long long)cells, (long long)qcap, d_err);
+                         qs.work.get(), qs.queue.get(), qs.visited.get(), static_cast<double*>(o), (long long)cells, (long long)qcap, d_err);
     else
       hipLaunchKernelGGL(vhp_queue_flood<float>, dim3(n), dim3(256), 0, stream, m.nx, m.ny, d_occ, d_src + 2 * (size_t)s0,
-                         qs.work, qs.queue, qs.visited, static_cast<float*>(o), (long long)cells, (long long)qcap, d_err);
+                         qs.work.get(), qs.queue.get(), qs.visited.get(), static_cast<float*>(o), (long long)cells, (long long)qcap, d_err);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;

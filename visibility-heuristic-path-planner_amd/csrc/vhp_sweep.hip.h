@@ -54,6 +54,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vhp_devbuf.hip.h"
 #include "vhp_diag.h"
 
 #include <algorithm>
@@ -984,19 +985,12 @@ __device__ __forceinline__ void y_strip(const DevMap& m, Emit& emit_, const Unit
 
 // Sweeps whose fronts exceed one round (rows_per_round = W*64*R) need 4 boundary rows per
 // workgroup in global memory; grows the caller's scratch as needed and points the map at it.
-inline hipError_t attach_round_scratch(DevMap& m, int rows_per_round, size_t n_workgroups, double** scratch, size_t* cap) {
+inline hipError_t attach_round_scratch(DevMap& m, int rows_per_round, size_t n_workgroups, DevBuf<double>& scratch) {
   const int maxdim = m.nx > m.ny ? m.nx : m.ny;
   if (maxdim <= rows_per_round) return hipSuccess;
   const size_t need = n_workgroups * 4 * (size_t)maxdim * sizeof(double);
-  if (*cap < need) {
-    if (*scratch) (void)hipFree(*scratch);
-    *scratch = nullptr;
-    *cap = 0;
-    hipError_t e = hipMalloc(scratch, need);
-    if (e != hipSuccess) return e;
-    *cap = need;
-  }
-  m.bnd = *scratch;
+  if (hipError_t e = scratch.grow(need); e != hipSuccess) return e;
+  m.bnd = scratch.get();
   m.bnd_len = maxdim;
   return hipSuccess;
 }

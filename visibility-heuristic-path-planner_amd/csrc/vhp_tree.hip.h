@@ -192,28 +192,11 @@ __global__ void __launch_bounds__(kTreeThreads) vhp_tree_goals(TreeGoalArgs a) {
 
 // The context's scratch of the tree calls: the tables, and the host forms' staging (goals in, results out).  Grow-only, freed with the
 // context.
+// (a free waits for whatever still reads the memory)
 struct TreeScratch {
-  char* tab = nullptr;
-  size_t tab_cap = 0;
-  char* io = nullptr;
-  size_t io_cap = 0;
+  DevBuf<char> tab;
+  DevBuf<char> io;
 };
-
-inline void tree_free(TreeScratch& s) {
-  if (s.tab) (void)hipFree(s.tab);
-  if (s.io) (void)hipFree(s.io);
-  s = TreeScratch{};
-}
-
-inline hipError_t tree_grow(char*& d, size_t& cap, size_t bytes) {
-  if (cap >= bytes) return hipSuccess;
-  if (d) (void)hipFree(d);   // (waits for whatever still reads it)
-  d = nullptr;
-  cap = 0;
-  if (hipError_t e = hipMalloc(&d, bytes); e != hipSuccess) return e;
-  cap = bytes;
-  return hipSuccess;
-}
 
 inline size_t tree_round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -227,9 +210,9 @@ inline hipError_t tree_tables(TreeScratch& s, const PathsDev& p, int q_first, in
   for (int q = q_first; q < q_first + n_q; ++q)
     if (p.slot[q] >= 0) { t->p.max_nb = std::max(t->p.max_nb, p.nb[q]); any = true; }
   const size_t entries = (size_t)n_q * ((size_t)t->p.max_nb + 1);
-  if (hipError_t e = tree_grow(s.tab, s.tab_cap, entries * 16); e != hipSuccess) return e;
-  t->cum = reinterpret_cast<double*>(s.tab);
-  t->parent = reinterpret_cast<uint32_t*>(s.tab + entries * 8);
+  if (hipError_t e = s.tab.grow(entries * 16); e != hipSuccess) return e;
+  t->cum = reinterpret_cast<double*>(s.tab.get());
+  t->parent = reinterpret_cast<uint32_t*>(s.tab.get() + entries * 8);
   t->depth = t->parent + entries;
   if (!any) return hipSuccess;
   hipLaunchKernelGGL(vhp_tree_tables, dim3(n_q), dim3(kTreeThreads), 0, stream, *t);
@@ -251,9 +234,9 @@ inline hipError_t tree_fields_launch(TreeScratch& s, const PathsDev& p, int q_fi
 inline hipError_t tree_fields_host(TreeScratch& s, const PathsDev& p, int q_first, int n_q, hipStream_t stream, double* length, uint32_t* n_path) {
   const size_t n = (size_t)n_q * p.nx * p.ny;
   const size_t len_bytes = length ? tree_round16(8 * n) : 0, bytes = len_bytes + (n_path ? 4 * n : 0);
-  if (hipError_t e = tree_grow(s.io, s.io_cap, bytes); e != hipSuccess) return e;
-  double* d_len = length ? reinterpret_cast<double*>(s.io) : nullptr;
-  uint32_t* d_cnt = n_path ? reinterpret_cast<uint32_t*>(s.io + len_bytes) : nullptr;
+  if (hipError_t e = s.io.grow(bytes); e != hipSuccess) return e;
+  double* d_len = length ? reinterpret_cast<double*>(s.io.get()) : nullptr;
+  uint32_t* d_cnt = n_path ? reinterpret_cast<uint32_t*>(s.io.get() + len_bytes) : nullptr;
   if (hipError_t e = tree_fields_launch(s, p, q_first, n_q, stream, d_len, d_cnt); e != hipSuccess) return e;
   if (length)
     if (hipError_t e = hipMemcpyAsync(length, d_len, 8 * n, hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
@@ -269,46 +252,22 @@ inline hipError_t tree_goals_launch(TreeScratch& s, const PathsDev& p, hipStream
   return hipGetLastError();
 }
 
-// The host form (every goal's q already checked against the solve): the goals go up, the launches run into staging, ONE copy of at
-// most n_goals * (8 * cap + 16) bytes comes back, one synchronisation; only the points of a goal whose status is VHP_OK reach the
-// caller's path_xy.
+// The host form (every goal's q already checked against the solve): the goals go up behind the staging of the results (PathStaging,
+// a row per goal), the launches run into it.
 inline hipError_t tree_goals_host(TreeScratch& s, const PathsDev& p, hipStream_t stream, const int32_t* goals, int n_goals, int32_t* path_xy,
                                   uint32_t cap, uint32_t* n_path, double* length, int32_t* status) {
   const size_t G = (size_t)n_goals;
-  uint32_t max_nb = 0;
-  for (int q = 0; q < p.n_queries; ++q)
-    if (p.slot[q] >= 0) max_nb = std::max(max_nb, p.nb[q]);
-  // (no path has more than max_nb + 2 points: room beyond that would only be copied; a path of more than `cap` points still exceeds
-  // the staging's room, as scap < cap only where no path reaches scap)
-  const uint32_t scap = path_xy ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)max_nb + 3) : 0;
-  const size_t head = 16 * G, out_bytes = tree_round16(head + 8 * (size_t)scap * G), bytes = out_bytes + 12 * G;
-  if (hipError_t e = tree_grow(s.io, s.io_cap, bytes); e != hipSuccess) return e;
-  int32_t* d_goals = reinterpret_cast<int32_t*>(s.io + out_bytes);
+  const PathStaging st(p, G, path_xy, cap);
+  const size_t out_bytes = tree_round16(st.bytes());
+  if (hipError_t e = s.io.grow(out_bytes + 12 * G); e != hipSuccess) return e;
+  int32_t* d_goals = reinterpret_cast<int32_t*>(s.io.get() + out_bytes);
   if (hipError_t e = hipMemcpyAsync(d_goals, goals, 12 * G, hipMemcpyHostToDevice, stream); e != hipSuccess) return e;
   TreeGoalArgs a{};
   a.goals = d_goals;
   a.n_goals = n_goals;
-  a.length = reinterpret_cast<double*>(s.io);
-  a.status = reinterpret_cast<int32_t*>(s.io + 8 * G);
-  a.n_path = reinterpret_cast<uint32_t*>(s.io + 12 * G);
-  a.path_xy = path_xy ? reinterpret_cast<int32_t*>(s.io + head) : nullptr;
-  a.cap = scap;
+  st.attach(a, s.io.get());
   if (hipError_t e = tree_goals_launch(s, p, stream, a); e != hipSuccess) return e;
-  const size_t back = head + 8 * (size_t)scap * G;
-  std::vector<char> h(back);
-  if (hipError_t e = hipMemcpyAsync(h.data(), s.io, back, hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
-  if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
-  const double* hl = reinterpret_cast<const double*>(h.data());
-  const int32_t* hs = reinterpret_cast<const int32_t*>(h.data() + 8 * G);
-  const uint32_t* hn = reinterpret_cast<const uint32_t*>(h.data() + 12 * G);
-  const int32_t* hp = reinterpret_cast<const int32_t*>(h.data() + head);
-  for (size_t g = 0; g < G; ++g) {
-    if (length) length[g] = hl[g];
-    if (status) status[g] = hs[g];
-    if (n_path) n_path[g] = hn[g];
-    if (path_xy && hs[g] == VHP_OK) std::copy(hp + 2 * g * scap, hp + 2 * g * scap + 2 * (size_t)hn[g], path_xy + 2 * g * (size_t)cap);
-  }
-  return hipSuccess;
+  return st.copy_out(s.io.get(), stream, path_xy, cap, n_path, length, status);
 }
 
 }  // namespace vhp
