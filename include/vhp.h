@@ -49,7 +49,8 @@ typedef enum vhp_status {
 typedef enum vhp_variant { VHP_SWEEP_FULL = 0, VHP_SWEEP_QUEUE = 1 } vhp_variant;
 
 /* element type of the STORED field; arithmetic is always IEEE binary64 */
-typedef enum vhp_dtype { VHP_F64 = 0, VHP_F32 = 1 } vhp_dtype;
+/* VHP_U8: one byte per cell, 1 = visible; only the ray-cast entry points (vhp_raycast_[maps_]batch[_device]) accept it */
+typedef enum vhp_dtype { VHP_F64 = 0, VHP_F32 = 1, VHP_U8 = 2 } vhp_dtype;
 
 #define VHP_MAX_SIDE 8192
 #define VHP_UNLABELLED 1000000000000000ULL /* (size_t)1e15, solver.cpp:46 */
@@ -302,6 +303,37 @@ int vhp_planner_goal_paths_device(vhp_ctx* ctx, int solve, const int32_t* d_goal
  * initialised to 1, solver.cpp:45).  Every write is a zero, so the union does not depend
  * on the order the rays are cast in and one thread per ray reproduces the reference. */
 int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host);
+
+/* Replaces the same double loop (solver.cpp:226-232 over raycasting(), :267-290) for a batch of sources in one call, where
+ * vhp_raycast_all takes one source, stores fp64 only and copies its field to the host every time.  Field i: nx*ny elements of `dtype`
+ * (VHP_F64, VHP_F32 or VHP_U8, the same 0 / 1 values) at out + i*nx*ny, always packed ("field_stride" is not applied); exactly what the
+ * reference leaves in visibilityRayCasting_ after a fresh reset() and that loop from source i -- for VHP_F64 the bytes of
+ * vhp_raycast_all.  That is more than "is the target visible": the first blocked cell a ray meets is zeroed together with the ray's
+ * target; a ray's own target is never tested, so a blocked cell in plain sight with nothing behind it (a blocked corner or border
+ * cell) stays 1; a blocked source zeroes every cell; a 1 x 1 grid stays 1.
+ * The kernels read the packed maps of vhp_set_map (x-major rays the column-packed copy, y-major rays the row-packed one), fill the
+ * fields with ones and then store only zeros.  A source outside the grid leaves its field 0, the others are cast, and the call
+ * returns VHP_ERR_SOURCE_OOB.  n_src = 0: VHP_OK, nothing launched.  No map set: VHP_ERR_NO_MAP; any other dtype: VHP_ERR_ARG.
+ * vhp_last_elapsed_ms: fill plus kernel (of the last slice of ~1 GiB of fields the host form stages). */
+int vhp_raycast_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int dtype, void* out_host);
+/* Device-resident form: device pointers, asynchronous on the context's stream; d_out aligned to its element type (else VHP_ERR_ARG).
+ * A rejected source's field is not written, and vhp_sync() reports VHP_ERR_SOURCE_OOB. */
+int vhp_raycast_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int dtype, void* d_out);
+/* The same loop run on a different environment per source: field i is cast from src_xy[2i..2i+1] on map map_idx[i] of the stack of
+ * vhp_set_maps -- what vhp_set_map(that map) + vhp_raycast_batch gives.  Errors as vhp_sweep_maps_batch's: a source outside the grid or
+ * a map index outside 0..n_maps-1 leaves its field 0 (device form: unwritten, reported by vhp_sync), the others are cast, the call
+ * returns VHP_ERR_SOURCE_OOB; no stack set: VHP_ERR_NO_MAP. */
+int vhp_raycast_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host);
+int vhp_raycast_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out);
+
+/* Replaces ONE call of raycasting(x0, y0, x1, y1) (solver.cpp:267-290), run for its answer only -- the reference offers the ray
+ * through its side effect on visibilityRayCasting_ alone.  Pair i is pairs_xyxy[4i..4i+3] = (x0, y0, x1, y1) on the map of
+ * vhp_set_map; hit_xy[2i..2i+1] is the first blocked cell the loop meets, or (-1, -1) where it reaches the target.  The target is
+ * never tested; the start is, so a pair with equal ends is clear.  An endpoint outside the grid gives (-2, -2), and the call (for the
+ * device form: vhp_sync) reports VHP_ERR_SOURCE_OOB with the other pairs answered.  n_pairs = 0: VHP_OK.  The single map only.  The
+ * device form takes device pointers (4-byte aligned) and is asynchronous on the context's stream. */
+int vhp_line_of_sight(vhp_ctx* ctx, const int32_t* pairs_xyxy, int n_pairs, int32_t* hit_xy);
+int vhp_line_of_sight_device(vhp_ctx* ctx, const int32_t* d_pairs_xyxy, int n_pairs, int32_t* d_hit_xy);
 
 /* MATLAB-flavoured variants.  The reference's MATLAB demos are a different algorithm from its C++ program:
  * MATLAB_code/visibility/getAccessibilityMap.m has an explicit diagonal rule (cell (i,i*1/fac) = alpha * its diagonal

@@ -32,6 +32,8 @@ VHP_ERR_NO_MAP = 101
 VHP_ERR_TOO_LARGE = 102
 SWEEP_FULL, SWEEP_QUEUE = 0, 1
 F64, F32 = 0, 1
+U8 = 2   # one byte per cell: the ray-cast calls only
+_DTYPES = {F64: np.float64, F32: np.float32, U8: np.uint8}
 UNLABELLED = 1000000000000000
 SOLVE_PLAIN, SOLVE_BATCH, SOLVE_MAPS_BATCH = 0, 1, 2   # vhp_solve_kind: whose tree the length-field and goal-path calls read
 _SOLVE_KINDS = {"plain": SOLVE_PLAIN, "batch": SOLVE_BATCH, "maps": SOLVE_MAPS_BATCH}
@@ -52,6 +54,8 @@ ABI_SYMBOLS = (
     "vhp_planner_batch_paths", "vhp_planner_batch_paths_device", "vhp_planner_maps_batch_paths", "vhp_planner_maps_batch_paths_device",
     "vhp_planner_path", "vhp_planner_path_device",
     "vhp_planner_length_fields", "vhp_planner_length_fields_device", "vhp_planner_goal_paths", "vhp_planner_goal_paths_device",
+    "vhp_raycast_batch", "vhp_raycast_batch_device", "vhp_raycast_maps_batch", "vhp_raycast_maps_batch_device",
+    "vhp_line_of_sight", "vhp_line_of_sight_device",
 )
 
 
@@ -121,6 +125,12 @@ def load_library():
     lib.vhp_planner_solve_variant.argtypes = [vp, i32, i32, i32, i32, f64, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
     lib.vhp_sweep_batch_offset.argtypes = [vp, vp, i32, f64, vp]
     lib.vhp_raycast_all.argtypes = [vp, i32, i32, vp]
+    lib.vhp_raycast_batch.argtypes = [vp, vp, i32, i32, vp]
+    lib.vhp_raycast_batch_device.argtypes = [vp, vp, i32, i32, vp]
+    lib.vhp_raycast_maps_batch.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.vhp_raycast_maps_batch_device.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.vhp_line_of_sight.argtypes = [vp, vp, i32, vp]
+    lib.vhp_line_of_sight_device.argtypes = [vp, vp, i32, vp]
     lib.vhp_timing.argtypes = [vp, i32]
     lib.vhp_timing_collect.argtypes = [vp, vp, i32, C.POINTER(i32)]
     lib.vhp_last_elapsed_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -544,6 +554,45 @@ class Context:
         out = np.empty((self.ny, self.nx), np.float64)
         self._check(self.lib.vhp_raycast_all(self.h, int(sx), int(sy), _ptr(out)))
         return out
+
+    def raycast_batch(self, sources, dtype=F64):
+        """vhp_raycast_batch: the reference's ray-cast field (a Bresenham ray to every cell) for each source in one call.  sources int32
+        [n, 2] (x, y) -> fields [n, ny, nx] of float64, float32 or uint8 (dtype F64 / F32 / U8), 1 = visible."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+        out = np.empty((len(src), self.ny, self.nx), _DTYPES[dtype])
+        self._check(self.lib.vhp_raycast_batch(self.h, _ptr(src), len(src), dtype, _ptr(out)))
+        return out
+
+    def raycast_batch_device(self, d_src, n_src, d_out, dtype=F64):
+        """Device-resident, asynchronous on the context stream.  d_src / d_out are raw device pointers; the fields are packed."""
+        self._check(self.lib.vhp_raycast_batch_device(self.h, C.c_void_p(d_src), n_src, dtype, C.c_void_p(d_out)))
+
+    def raycast_maps_batch(self, sources, map_index, dtype=F64):
+        """vhp_raycast_maps_batch: raycast_batch across the stack of set_maps -- source i on map map_index[i] -> fields [n, maps_ny, maps_nx]."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+        idx = np.ascontiguousarray(map_index, np.int32).reshape(-1)
+        if len(idx) != len(src):
+            raise ValueError("raycast_maps_batch: %d sources but %d map indices" % (len(src), len(idx)))
+        out = np.empty((len(src), self.maps_ny, self.maps_nx), _DTYPES[dtype])
+        self._check(self.lib.vhp_raycast_maps_batch(self.h, _ptr(src), _ptr(idx), len(src), dtype, _ptr(out)))
+        return out
+
+    def raycast_maps_batch_device(self, d_src, d_map, n_src, d_out, dtype=F64):
+        """Device-resident, asynchronous on the context stream.  d_src / d_map / d_out are raw device pointers."""
+        self._check(self.lib.vhp_raycast_maps_batch_device(self.h, C.c_void_p(d_src), C.c_void_p(d_map), n_src, dtype, C.c_void_p(d_out)))
+
+    def line_of_sight(self, pairs):
+        """vhp_line_of_sight: pairs int32 [n, 4] rows (x0, y0, x1, y1) -> int32 [n, 2]: the first blocked cell on the reference's ray from
+        (x0, y0) to (x1, y1) (the start is tested, the target is not), or (-1, -1) where the segment is clear.  A pair with an end outside
+        the grid raises VhpError (VHP_ERR_SOURCE_OOB); the C call marks such rows (-2, -2) and answers the others."""
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 4)
+        hit = np.empty((len(p), 2), np.int32)
+        self._check(self.lib.vhp_line_of_sight(self.h, _ptr(p), len(p), _ptr(hit)))
+        return hit
+
+    def line_of_sight_device(self, d_pairs, n_pairs, d_hit):
+        """Device-resident, asynchronous on the context stream.  d_pairs (int32 [n, 4]) / d_hit (int32 [n, 2]) are raw device pointers."""
+        self._check(self.lib.vhp_line_of_sight_device(self.h, C.c_void_p(d_pairs), n_pairs, C.c_void_p(d_hit)))
 
     def reconstruct_path(self, came_from, pivots, end):
         return reconstruct_path(came_from, pivots, end)

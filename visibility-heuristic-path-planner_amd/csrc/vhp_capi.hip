@@ -26,6 +26,7 @@
 #include "vhp_paths.hip.h"
 #include "vhp_tree.hip.h"
 #include "vhp_queue.hip.h"
+#include "vhp_raycast_launch.h"
 #include "vhp_variant.hip.h"
 #include "vhp_union.hip.h"
 
@@ -648,6 +649,68 @@ int goal_paths(vhp_ctx* ctx, const char* who, bool device, int solve, const int3
   return VHP_OK;
 }
 
+// ---- ray casting for batches of sources (vhp_raycast.hip): what the entry points below share
+size_t raycast_elem_bytes(int dtype) { return dtype == VHP_F64 ? 8 : dtype == VHP_F32 ? 4 : dtype == VHP_U8 ? 1 : 0; }
+
+vhp::PackedOcc packed_occ(const vhp::PackedMaps& p) { return {p.rows.get(), p.cols.get(), p.wpr, p.wpc}; }
+
+// The device form on the single map (d_map_idx null) or on the stack: packed fields, timed as vhp_raycast_all is (fill plus kernel).
+int raycast_device(vhp_ctx* ctx, const char* who, bool maps, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out) {
+  if (!ctx || !d_src_xy || !d_out || n_src < 0 || (maps && !d_map_idx)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
+  const vhp::PackedMaps& m = maps ? ctx->maps : ctx->map;
+  if (!m.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + (maps ? ": no maps set" : ": no map set"));
+  const size_t esz = raycast_elem_bytes(dtype);
+  if (!esz) return fail(ctx, VHP_ERR_ARG, "bad dtype");
+  if (reinterpret_cast<uintptr_t>(d_out) % esz != 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": d_out is not aligned to its element type");
+  if (n_src == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  vhp::RaycastLaunch l;
+  l.d_out = d_out;
+  l.dtype = dtype;
+  l.d_src_xy = d_src_xy;
+  l.n_src = n_src;
+  l.nx = m.nx;
+  l.ny = m.ny;
+  l.occ = packed_occ(m);
+  l.d_map_idx = d_map_idx;
+  l.n_maps = m.n;
+  l.rows_stride = (long long)m.ny * m.wpr;
+  l.cols_stride = (long long)m.nx * m.wpc;
+  l.d_err = ctx->d_err.get();
+  l.stream = ctx->stream;
+  const hipError_t e = vhp::launch_raycast(l);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  return VHP_OK;
+}
+
+// The host form: slices through the context's scratch like the sweeps; a source that is not cast leaves its field 0.
+int raycast_host(vhp_ctx* ctx, const char* who, bool maps, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host) {
+  if (!ctx || !src_xy || !out_host || n_src < 0 || (maps && !map_idx)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
+  const vhp::PackedMaps& m = maps ? ctx->maps : ctx->map;
+  if (!m.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + (maps ? ": no maps set" : ": no map set"));
+  const size_t esz = raycast_elem_bytes(dtype);
+  if (!esz) return fail(ctx, VHP_ERR_ARG, "bad dtype");
+  const size_t field = (size_t)m.nx * m.ny * esz;
+  int rc = stage_slices(ctx, who, src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
+    if (maps) {
+      const hipError_t e = ctx->d_map_idx.grow((size_t)n * sizeof(int32_t));
+      if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
+      VHP_HIP(hipMemcpyAsync(ctx->d_map_idx.get(), map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return raycast_device(ctx, who, maps, ctx->d_src.get(), maps ? ctx->d_map_idx.get() : nullptr, n, dtype, ctx->d_out.get());
+  });
+  if (rc != VHP_OK || n_src == 0) return rc;
+  rc = vhp_sync(ctx);
+  // (the kernels leave such a field unwritten: zero here, not what the scratch held)
+  for (int i = 0; i < n_src; ++i)
+    if (!vhp::raycast_source_ok(src_xy, maps ? map_idx : nullptr, i, m.nx, m.ny, m.n))
+      std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -861,6 +924,51 @@ int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
   VHP_HIP(hipMemcpyAsync(out_host, d, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   return VHP_OK;
+}
+
+// ---- ray casting for batches of sources, and line of sight (vhp_raycast.hip) ------------------------------------------------------
+int vhp_raycast_batch(vhp_ctx* ctx, const int32_t* src_xy, int n_src, int dtype, void* out_host) {
+  return raycast_host(ctx, "vhp_raycast_batch", false, src_xy, nullptr, n_src, dtype, out_host);
+}
+int vhp_raycast_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, int dtype, void* d_out) {
+  return raycast_device(ctx, "vhp_raycast_batch_device", false, d_src_xy, nullptr, n_src, dtype, d_out);
+}
+int vhp_raycast_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map_idx, int n_src, int dtype, void* out_host) {
+  return raycast_host(ctx, "vhp_raycast_maps_batch", true, src_xy, map_idx, n_src, dtype, out_host);
+}
+int vhp_raycast_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out) {
+  return raycast_device(ctx, "vhp_raycast_maps_batch_device", true, d_src_xy, d_map_idx, n_src, dtype, d_out);
+}
+
+int vhp_line_of_sight_device(vhp_ctx* ctx, const int32_t* d_pairs_xyxy, int n_pairs, int32_t* d_hit_xy) {
+  if (!ctx || !d_pairs_xyxy || !d_hit_xy || n_pairs < 0) return fail(ctx, VHP_ERR_ARG, "vhp_line_of_sight_device: bad argument");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_line_of_sight_device: no map set");
+  if ((reinterpret_cast<uintptr_t>(d_pairs_xyxy) | reinterpret_cast<uintptr_t>(d_hit_xy)) & 3)
+    return fail(ctx, VHP_ERR_ARG, "vhp_line_of_sight_device: a buffer is not aligned to its element type");
+  if (n_pairs == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  const hipError_t e = vhp::launch_line_of_sight(packed_occ(ctx->map), ctx->map.nx, ctx->map.ny, d_pairs_xyxy, n_pairs, d_hit_xy, ctx->d_err.get(), ctx->stream);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_line_of_sight_device: ") + hipGetErrorString(e));
+  VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  return VHP_OK;
+}
+
+int vhp_line_of_sight(vhp_ctx* ctx, const int32_t* pairs_xyxy, int n_pairs, int32_t* hit_xy) {
+  if (!ctx || !pairs_xyxy || !hit_xy || n_pairs < 0) return fail(ctx, VHP_ERR_ARG, "vhp_line_of_sight: bad argument");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_line_of_sight: no map set");
+  if (n_pairs == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  // (pairs in the source scratch, hits in the output scratch: 16 and 8 bytes a pair, one copy each way)
+  hipError_t e = ctx->d_src.grow((size_t)n_pairs * 4 * sizeof(int32_t));
+  if (e == hipSuccess) e = ctx->d_out.grow((size_t)n_pairs * 2 * sizeof(int32_t));
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_line_of_sight: scratch: ") + hipGetErrorString(e));
+  VHP_HIP(hipMemcpyAsync(ctx->d_src.get(), pairs_xyxy, (size_t)n_pairs * 4 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = vhp_line_of_sight_device(ctx, ctx->d_src.get(), n_pairs, static_cast<int32_t*>(ctx->d_out.get()));
+  if (rc != VHP_OK) return rc;
+  VHP_HIP(hipMemcpyAsync(hit_xy, ctx->d_out.get(), (size_t)n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  return vhp_sync(ctx);
 }
 
 // ---- max-union + arg-source of a batch of fields (vhp_union.hip.h) ---------------------------------------------------
