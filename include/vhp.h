@@ -358,21 +358,43 @@ int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x,
  * image.  fp64 fields, host buffers, cells the reference never writes are 0, grid sides up to 4096. */
 int vhp_sweep_batch_offset(vhp_ctx* ctx, const int32_t* src_xy, int n_src, double offset, double* out_host);
 
-/* Elapsed milliseconds between the first and last kernel of the most recent
- * vhp_sweep_batch_device / planner call, from hipEvents recorded on the context
- * stream.  Blocks until that work has finished.  vhp_probe_stores and vhp_alloc_output time their probes with the same pair of
- * events: after either of them there is nothing to report (VHP_ERR_ARG, "nothing timed yet") until the next sweep or solve.
- * The events carry no system-scope fence (hipEventDisableSystemFence): the call reports a time and is no point behind which the
- * host may read what the work wrote -- that is vhp_sync, hipStreamSynchronize or a copy on the stream. */
+/* Elapsed milliseconds of the most recent vhp_sweep_batch_device / planner call on the device.  How it is measured depends on
+ * what the call launched:
+ *  - the pool sweep and the latency sweep (vhp_last_sweep_kernel 3 and 4) time themselves: the launch's own kernels write
+ *    timestamps of the device's constant-rate clock -- thread 0 of the launch's first kernel as its first act (the unit-ordering
+ *    pre-kernel; every workgroup of a latency launch that has none), every workgroup of the sweep kernel when its wavefronts are
+ *    done and their stores have landed -- and the time is the first of the first kernel's to the last workgroup's last.  Nothing is
+ *    recorded on the stream for such a launch: it costs the launches around it no barrier packet.  The time holds no dispatch of
+ *    either kernel, so it reads a few microseconds less than a pair of events around the same launch;
+ *  - everything else -- the front sweep (vhp_last_sweep_kernel 1, and every vhp_sweep_maps_batch), the queue variant, ray casting
+ *    and line of sight, the planner solves (one time around a whole solve), and a latency launch that would write more timestamps
+ *    than two per CU of the device (a slot's size) -- is timed by two hipEvents recorded on the context stream around it, first
+ *    kernel to last.  A library built with -DVHP_TIMING_STAMPS=0 times every launch this way.
+ * The call blocks until that work has finished: it synchronises the stream the launch went out on (hipStreamSynchronize; for the
+ * events, hipEventSynchronize) and, for a stamped launch, copies its timestamps to the host.  vhp_probe_stores and vhp_alloc_output
+ * time their probes with the context's pair of events: after either of them there is nothing to report (VHP_ERR_ARG, "nothing timed
+ * yet") until the next sweep or solve.  A launch whose timestamps cannot be read (VHP_ERR_HIP) did not finish or did not run.
+ * The events carry no system-scope fence (hipEventDisableSystemFence): the call reports a time and is no point behind which the host
+ * may read what the work wrote -- that is vhp_sync, hipStreamSynchronize or a copy on the stream. */
 int vhp_last_elapsed_ms(vhp_ctx* ctx, float* ms);
 
-/* Per-launch kernel timing for benchmarks.  vhp_timing(ctx, 1) makes every following
- * vhp_sweep_batch_device call bracket what it launches -- the unit-ordering pre-kernel and the
- * sweep kernel -- with a pair of hipEvents on the context stream; vhp_timing_collect waits for them,
- * writes up to `cap` durations in milliseconds (oldest first), returns their count in *n and
- * clears the list.  vhp_timing(ctx, 0) switches it off.  These events carry no system-scope fence (hipEventDisableSystemFence:
- * recording one costs the launches around it no cache write-back) and are for timing only: waiting for them orders no memory. */
-int vhp_timing(vhp_ctx* ctx, int enable);  /* enable > 1: also pre-creates that many event pairs */
+/* Per-launch kernel timing for benchmarks.  vhp_timing(ctx, n), n >= 1, makes every following vhp_sweep_batch_device /
+ * vhp_sweep_maps_batch_device call time what it launches -- the unit-ordering pre-kernel and the sweep kernel --; vhp_timing_collect
+ * waits for the launches, writes up to `cap` durations in milliseconds (oldest first), returns their count in *n and clears the list.
+ * vhp_timing(ctx, 0) switches it off.
+ * A pool-sweep or latency-sweep launch is timed by the timestamps its own kernels write (vhp_last_elapsed_ms above: first stamp of
+ * the launch's first kernel to last stamp of its last workgroup); no event is recorded for it, with vhp_timing on or off.  Its
+ * timestamps go to one slot of a ring on the device that vhp_timing(ctx, n) sizes for n launches between two vhp_timing_collect
+ * calls (n = 1: 64; the ring only grows, and only while no timed launch waits to be collected; it is allocated here, never inside a
+ * launch).  The same slot serves vhp_last_elapsed_ms: for such a launch it and the launch's entry of vhp_timing_collect are the same
+ * number, bit for bit.  A timed launch that finds the ring full is timed as every other kernel's launch is: by a pair of hipEvents
+ * on the context stream around it (n > 1 also pre-creates n such pairs), inside the pair vhp_last_elapsed_ms reads.
+ * vhp_timing_collect synchronises the stream(s) the stamped launches went out on (hipStreamSynchronize), copies the ring's slots to
+ * the host in one copy (two where they wrap), and waits for the event pairs of the others (hipEventSynchronize).  A launch whose
+ * time cannot be read -- timestamps of another launch in its slot, a pair that was never recorded -- is dropped and counted in the
+ * error the call returns (VHP_ERR_HIP).  The events carry no system-scope fence (hipEventDisableSystemFence: recording one costs the
+ * launches around it no cache write-back) and are for timing only: waiting for them orders no memory. */
+int vhp_timing(vhp_ctx* ctx, int enable);  /* enable > 1: the ring's slots and the event pairs for that many timed launches */
 int vhp_timing_collect(vhp_ctx* ctx, float* ms_out, int cap, int* n);
 
 /* Launch-shape overrides for tuning and for parity tests that must reach every compiled shape

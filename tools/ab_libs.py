@@ -5,8 +5,9 @@ keys, e.g. -@kernel=1 exp/libvhp_NOSTORE.so@kernel=2, or the launch shapes: -@ro
 Set AB_DTYPE=f32 in the environment for fp32 fields.
 With --wall in front of <side>: wall clock instead -- per alternation 200 launches (AB_STEPS) back to back with vhp_timing on, as
 bench.py's timed region runs them, between two synchronizes; six alternations count (AB_REPS, the first one more is dropped).  Prints
-per build the median and the range of the wall time per launch, of the event-pair time and of their difference, and whether every
-run of each later build beat every run of the first one."""
+per build the median and the range of the wall time per launch, of the time vhp_timing_collect reports (event pairs, or the launches'
+own stamps) and of their difference, and whether every run of each later build beat every run of the first one.  AB_TIMING=0 in the
+environment: the same with vhp_timing off (wall clock alone)."""
 import os, sys, time
 WALL = len(sys.argv) > 1 and sys.argv[1] == "--wall"
 if WALL:
@@ -45,29 +46,35 @@ for lib in libs:
     ctxs.append(c)
 def wall_ab():
     steps, reps = int(os.environ.get("AB_STEPS", "200")), int(os.environ.get("AB_REPS", "6"))
+    timing = os.environ.get("AB_TIMING", "1") != "0"
     dt = mod.F32 if F32 else mod.F64
-    wall, kern = {l: [] for l in libs}, {l: [] for l in libs}
+    wall, kern, med = {l: [] for l in libs}, {l: [] for l in libs}, {l: [] for l in libs}
     for rep in range(reps + 1):
         for lib, ctx in zip(libs, ctxs):
             for _ in range(5):
                 ctx.sweep_batch_device(d_src.data_ptr(), n, out.data_ptr(), dtype=dt)
             torch.cuda.synchronize()
-            ctx.timing(True, prealloc=steps + 2)
+            if timing:
+                ctx.timing(True, prealloc=steps + 2)
             t0 = time.perf_counter()
             for _ in range(steps):
                 ctx.sweep_batch_device(d_src.data_ptr(), n, out.data_ptr(), dtype=dt)
             torch.cuda.synchronize()
             el = time.perf_counter() - t0
-            k = ctx.timing_collect(steps)
+            k = ctx.timing_collect(steps) if timing else np.full(steps, np.nan, np.float32)
             ctx.timing(False)
             if rep:
                 wall[lib].append(el / steps * 1e6)
                 kern[lib].append(float(k.sum()) / steps * 1e3)
+                med[lib].append(float(np.median(k)) * 1e3)
     fmt = lambda v: "median %.1f (%.1f .. %.1f)" % (np.median(v), min(v), max(v))
     for lib in libs:
         gap = [w - k for w, k in zip(wall[lib], kern[lib])]
-        print("side %d n %d lib [%s], us per launch over %d x %d launches: wall %s; event pairs %s; wall - pairs %s" % (
-            side, n, lib, len(wall[lib]), steps, fmt(wall[lib]), fmt(kern[lib]), fmt(gap)))
+        if not timing:
+            print("side %d n %d lib [%s], vhp_timing off, us per launch over %d x %d launches: wall %s" % (side, n, lib, len(wall[lib]), steps, fmt(wall[lib])))
+        else:
+            print("side %d n %d lib [%s], us per launch over %d x %d launches: wall %s; timing_collect %s; wall - collect %s; median launch by timing_collect %s" % (
+                side, n, lib, len(wall[lib]), steps, fmt(wall[lib]), fmt(kern[lib]), fmt(gap), fmt(med[lib])))
         print("    wall by alternation: %s" % " ".join("%.1f" % x for x in wall[lib]))
     for lib in libs[1:]:
         print("[%s] against [%s]: %s; medians %.1f against %.1f us (%+.2f %%)" % (

@@ -274,7 +274,8 @@ class Context:
         return int(self.lib.vhp_last_sweep_kernel(self.h))
 
     def timing(self, enable=True, prealloc=0):
-        """prealloc > 1: event pairs created now, so that launches inside a timed loop create none."""
+        """prealloc > 1: room for that many timed launches made now (slots for the timestamps the pool and latency sweeps write, event
+        pairs for the other kernels), so that launches inside a timed loop allocate and create nothing."""
         self._check(self.lib.vhp_timing(self.h, max(int(prealloc), 1) if enable else 0))
 
     def timing_collect(self, cap=4096):

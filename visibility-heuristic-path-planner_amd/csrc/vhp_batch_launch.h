@@ -8,6 +8,7 @@
 
 #include "vhp_devbuf.hip.h"
 #include "vhp_launch_plan.hpp"
+#include "vhp_stamps.hpp"
 
 namespace vhp {
 
@@ -58,8 +59,11 @@ struct BatchArgs {
   // called with (kernel, bytes) before a launch that needs more than the default dynamic LDS: the per-device
   // bookkeeping lives with the context
   std::function<hipError_t(const void*, size_t)> raise_lds;
-  // optional per-launch timing events, recorded around the sweep kernel only
-  hipEvent_t ev_begin, ev_end;
+  // optional per-launch timing events, recorded around the launch's kernels (a timed launch that has no slot for its timestamps)
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  // ... or the launch's slot for the timestamps its own kernels write, tagged pool_epoch (vhp_stamps.hpp; pool_stamp_counts /
+  // lat_stamp_counts entries of it: vhp_launch_plan.hpp); null: the kernels write none.  Plain launches only: a planner's loop passes none.
+  stamps::Entry* d_stamps = nullptr;
   PoolOpts pool;          // pool sweep: the vhp_set_option keys of its launch plan (vhp_launch_plan.hpp plan_pool)
   LatLaunch lat;          // latency sweep: the launch of a planner's loop
   unsigned long long pool_epoch = 0;  // pool sweep: the tag of this launch's boundary-line entries: never 0, never reused on this scratch

@@ -27,6 +27,7 @@
 #include "vhp_tree.hip.h"
 #include "vhp_queue.hip.h"
 #include "vhp_raycast_launch.h"
+#include "vhp_stamps.hpp"
 #include "vhp_variant.hip.h"
 #include "vhp_union.hip.h"
 
@@ -35,7 +36,7 @@ struct vhp_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
+  vhp::stamps::Last timed;  // what vhp_last_elapsed_ms reports: nothing, ev0 / ev1, or the stamps of a pool- or latency-sweep launch
   std::string err;
 
   int n_cus = 256;
@@ -57,9 +58,19 @@ struct vhp_ctx {
   vhp::DevBuf<int> d_lat_order;  // launch order of the latency sweep's units where it launches more of them than the device has CUs
   vhp::DevBuf<int> d_pool;       // pool sweep: pull counter, unit order, diagonal lines, tagged boundary lines (zeroed when allocated)
   unsigned long long pool_epoch = 0x5A17000000000000ull;  // tag of the last pool launch
-  bool timing = false;      // per-launch event pairs around the sweep kernel (vhp_timing)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed_launches;
+  bool timing = false;      // every sweep launch is timed (vhp_timing): by the stamps its kernels write, else by an event pair around it
+  struct TimedLaunch {      // ... one or the other
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    vhp::stamps::Launch st;
+  };
+  std::vector<TimedLaunch> timed_launches;  // oldest first
   std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;  // recycled pairs: no hipEventCreate inside a timed loop
+  // the stamps (vhp_stamps.hpp): slot 0 for the launches with vhp_timing off, then vhp_timing's ring; allocated by vhp_create and
+  // vhp_timing, never inside a launch
+  vhp::DevBuf<vhp::stamps::Entry> d_stamps;
+  std::vector<vhp::stamps::Entry> h_stamps;  // their host copy, slot by slot
+  vhp::stamps::Ring ring;
+  int clock_khz = 0;        // rate of the clock the stamps read (hipDeviceAttributeWallClockRate); 0: no stamps, events everywhere
 
   // launch-shape overrides (vhp_set_option); 0 / -1 = automatic
   int opt_rows_per_lane = 0;  // R: 1, 2 or 4
@@ -188,7 +199,15 @@ std::vector<double> recip_table(int nx, int ny) {
 struct LaunchOpts {
   long long field_stride = 0;  // elements from one field to the next (0: nx * ny, packed)
   bool timed = false;
+  // a pool- or latency-sweep launch that writes its own timestamps: the slot the entry point took for it (take_stamp_slot); the launch
+  // fills in its tag.  Null: timed by events, if at all.
+  vhp::stamps::Launch* stamp = nullptr;
 };
+
+// -DVHP_TIMING_STAMPS=0: no launch writes timestamps, event records time every one of them (an A/B build, tools/ab_libs.py)
+#ifndef VHP_TIMING_STAMPS
+#define VHP_TIMING_STAMPS 1
+#endif
 
 // The library's timing events -- the context's ev0 / ev1 and vhp_timing's pairs -- carry no system-scope fence.  A plain hipEvent
 // releases to the system when it is recorded: a cache write-back and invalidate between one launch's sweep and the next launch's
@@ -215,7 +234,56 @@ hipError_t acquire_events(vhp_ctx* c, bool timed, EventPair* ev) {
 }
 // ... timed if the launch went out; back to the pool if it failed (a pair that was never recorded can never be waited for)
 void release_events(vhp_ctx* c, const EventPair& ev, hipError_t launched) {
-  if (ev.first) (launched == hipSuccess ? c->timed_launches : c->event_pool).push_back(ev);
+  if (!ev.first) return;
+  if (launched == hipSuccess) c->timed_launches.push_back({ev, {}});
+  else c->event_pool.push_back(ev);
+}
+
+// The stamps' device array for the ring as it is now: (re)allocated and zeroed, with its host copy.  Not inside a launch: hipMalloc
+// and hipFree wait for the device.  A failure leaves no array, and with it no stamped launches.
+hipError_t allocate_stamps(vhp_ctx* c) {
+  hipError_t e = c->d_stamps.grow(c->ring.bytes());
+  if (e == hipSuccess) e = hipMemsetAsync(c->d_stamps.get(), 0, c->ring.bytes(), c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { c->d_stamps.reset(); return e; }
+  c->h_stamps.assign(c->ring.bytes() / sizeof(vhp::stamps::Entry), vhp::stamps::Entry{0, 0});
+  return hipSuccess;
+}
+
+// The slot for the timestamps of a plain launch of n_src sources by the pool sweep (kernel 3) or the latency sweep (kernel 4): one
+// of the ring's if the launch is timed, slot 0 if not; .slot = -1 where the launch is timed by events -- another kernel, no clock, a
+// launch of more workgroups than a slot has entries for, the ring full.
+vhp::stamps::Launch take_stamp_slot(vhp_ctx* c, int kernel, int n_src, bool timed) {
+  vhp::stamps::Launch st;
+  if (!VHP_TIMING_STAMPS || (kernel != 3 && kernel != 4) || c->clock_khz <= 0 || !c->d_stamps.get()) return st;
+  const vhp::StampCounts sc = kernel == 4 ? vhp::lat_stamp_counts(vhp::plan_lat(c->map.nx, c->map.ny, n_src, c->n_cus, false, c->opt_lat_workgroups, {true}), n_src)
+                                          : vhp::pool_stamp_counts(c->n_cus);
+  if (!c->ring.fits(sc.n_begin, sc.n_end)) return st;
+  st.slot = timed ? c->ring.take() : 0;
+  st.n_begin = sc.n_begin;
+  st.n_end = sc.n_end;
+  st.stream = c->stream;
+  return st;
+}
+
+// The host copy of the `count` slots from `first` on.
+hipError_t copy_stamp_slots(vhp_ctx* c, int first, int count) {
+  const size_t at = c->ring.slot_offset(first);
+  return hipMemcpy(c->h_stamps.data() + at, c->d_stamps.get() + at, (size_t)count * vhp::stamps::slot_bytes(c->ring.groups()), hipMemcpyDeviceToHost);
+}
+
+// vhp_last_elapsed_ms's stamped launch, read: its stream synchronised, its entries copied and reduced (Last::kStamps -> kRead).
+void read_last_stamps(vhp_ctx* c) {
+  if (c->timed.state != vhp::stamps::Last::kStamps) return;
+  const vhp::stamps::Launch l = c->timed.launch;
+  vhp::stamps::Time t;
+  const size_t at = c->ring.slot_offset(l.slot);
+  if (hipStreamSynchronize(static_cast<hipStream_t>(l.stream)) == hipSuccess &&
+      hipMemcpy(c->h_stamps.data() + at, c->d_stamps.get() + at, (size_t)(l.n_begin + l.n_end) * sizeof(vhp::stamps::Entry), hipMemcpyDeviceToHost) == hipSuccess)
+    t = vhp::stamps::reduce(c->h_stamps.data() + at, l, c->clock_khz);
+  else
+    (void)hipGetLastError();
+  c->timed.read(l.tag, t);
 }
 
 // What sweeps a batch of n_src sources on m's grid with the context's options (vhp_choice.hpp), or with `kernel` in place of the option.
@@ -320,8 +388,14 @@ hipError_t launch_batch_sweep(vhp_ctx* c, const vhp::PackedMaps& m, const int32_
   a.stream = c->stream;
   a.raise_lds = [c](const void* fn, size_t bytes) { return raise_lds_limit(c, fn, bytes); };
   a.pool = c->opt_pool;
+  // timed by its own kernels' stamps in the slot the entry point took, tagged with the launch's epoch -- or by an event pair
+  const bool stamped = o.stamp && o.stamp->stamped();
+  if (stamped) {
+    o.stamp->tag = a.pool_epoch;
+    a.d_stamps = c->d_stamps.get() + c->ring.slot_offset(o.stamp->slot);
+  }
   EventPair ev;
-  if (hipError_t ee = acquire_events(c, o.timed, &ev); ee != hipSuccess) return ee;
+  if (hipError_t ee = acquire_events(c, o.timed && !stamped, &ev); ee != hipSuccess) return ee;
   a.ev_begin = ev.first;
   a.ev_end = ev.second;
   const hipError_t e = lat ? vhp::launch_lat(a) : vhp::launch_pool(a);
@@ -512,7 +586,7 @@ int planner_call(vhp_ctx* ctx, const char* who, int n_src, size_t n_workgroups, 
   ctx->pl.path_state = 0;
   const int rc = solve(pm, plan, &msg);
   note_unsolved(ctx, rc);
-  ctx->timed = true;
+  ctx->timed.events();
   if (rc != VHP_OK) ctx->err = msg;
   return rc;
 }
@@ -682,7 +756,7 @@ int raycast_device(vhp_ctx* ctx, const char* who, bool maps, const int32_t* d_sr
   const hipError_t e = vhp::launch_raycast(l);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
+  ctx->timed.events();
   return VHP_OK;
 }
 
@@ -737,6 +811,15 @@ int vhp_create(int device_ordinal, vhp_ctx** out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) ctx->n_cus = prop.multiProcessorCount;
   }
+  // the stamps' clock and slot 0 (the launches with vhp_timing off); a slot holds a launch of up to one workgroup per CU.  Without the
+  // clock's rate, or without the memory, no launch is stamped: the events time them all.
+  if (VHP_TIMING_STAMPS) {
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_ordinal) == hipSuccess && khz > 0) ctx->clock_khz = khz;
+    else (void)hipGetLastError();
+    ctx->ring.resize(0, ctx->n_cus);
+    if (ctx->clock_khz > 0 && allocate_stamps(ctx) != hipSuccess) (void)hipGetLastError();
+  }
   *out = ctx;
   return VHP_OK;
 }
@@ -747,7 +830,8 @@ int vhp_destroy(vhp_ctx* ctx) {
   hipStreamSynchronize(ctx->stream);
   free_map(ctx);
   free_maps(ctx);
-  for (auto& pr : ctx->timed_launches) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+  for (auto& t : ctx->timed_launches)
+    if (t.ev.first) { (void)hipEventDestroy(t.ev.first); (void)hipEventDestroy(t.ev.second); }
   for (auto& pr : ctx->event_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (void* p : ctx->placed) (void)hipFree(p);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
@@ -804,18 +888,36 @@ static int sweep_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, int n_src, 
     return fail(ctx, VHP_ERR_ARG, "vhp_sweep_batch_device: the queue variant writes packed fields (field_stride must be 0)");
   if (n_src == 0) return VHP_OK;
   VHP_ON_DEVICE(ctx);
-  VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  // A pool- or latency-sweep launch times itself by the stamps its kernels write, and nothing is recorded on the stream for it; every
+  // other launch -- and one of those two that has no slot for its stamps -- between ev0 and ev1 (and vhp_timing's pair inside).
+  vhp::stamps::Launch st = take_stamp_slot(ctx, variant == VHP_SWEEP_QUEUE ? 0 : plan_for(ctx, n_src, dtype == VHP_F64).kernel, n_src, o.timed);
+  LaunchOpts lo = o;
+  lo.stamp = &st;
+  const bool ring_slot = st.slot > 0;
+  if (!st.stamped()) {
+    // (ev0 moves before the launch is known to go out: from here on the old pair says nothing, whatever happens below)
+    if (ctx->timed.state == vhp::stamps::Last::kEvents) ctx->timed.nothing();
+    VHP_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  }
   hipError_t e;
   if (variant == VHP_SWEEP_QUEUE) {
     e = vhp::launch_queue_sweep_impl(ctx->qs, dev_map(ctx->map), ctx->d_occ.get(), d_src_xy, n_src, dtype, d_out, ctx->d_err.get(), ctx->stream);
   } else if (dtype == VHP_F64) {
-    e = launch_sweep<double>(ctx, d_src_xy, n_src, static_cast<double*>(d_out), o);
+    e = launch_sweep<double>(ctx, d_src_xy, n_src, static_cast<double*>(d_out), lo);
   } else {
-    e = launch_sweep<float>(ctx, d_src_xy, n_src, static_cast<float*>(d_out), o);
+    e = launch_sweep<float>(ctx, d_src_xy, n_src, static_cast<float*>(d_out), lo);
   }
-  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) {  // (its slot back to the ring; what vhp_last_elapsed_ms reports stays what it was)
+    if (ring_slot) ctx->ring.untake();
+    return fail(ctx, VHP_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(e));
+  }
+  if (st.stamped()) {
+    if (ring_slot) ctx->timed_launches.push_back({{nullptr, nullptr}, st});
+    ctx->timed.stamps(st);
+    return VHP_OK;
+  }
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
+  ctx->timed.events();
   return VHP_OK;
 }
 
@@ -876,7 +978,7 @@ static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const 
                                         : launch_maps_sweep<float>(ctx, d_src_xy, d_map_idx, n_src, static_cast<float*>(d_out), o);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("maps sweep launch: ") + hipGetErrorString(e));
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
+  ctx->timed.events();
   return VHP_OK;
 }
 
@@ -920,7 +1022,7 @@ int vhp_raycast_all(vhp_ctx* ctx, int src_x, int src_y, double* out_host) {
   hipLaunchKernelGGL(vhp::vhp_raycast, dim3(blocks), dim3(256), 0, ctx->stream, ctx->map.nx, ctx->map.ny, ctx->d_occ.get(), src_x, src_y, d);
   VHP_HIP(hipGetLastError());
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
+  ctx->timed.events();
   VHP_HIP(hipMemcpyAsync(out_host, d, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   return VHP_OK;
@@ -951,7 +1053,7 @@ int vhp_line_of_sight_device(vhp_ctx* ctx, const int32_t* d_pairs_xyxy, int n_pa
   const hipError_t e = vhp::launch_line_of_sight(packed_occ(ctx->map), ctx->map.nx, ctx->map.ny, d_pairs_xyxy, n_pairs, d_hit_xy, ctx->d_err.get(), ctx->stream);
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_line_of_sight_device: ") + hipGetErrorString(e));
   VHP_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = true;
+  ctx->timed.events();
   return VHP_OK;
 }
 
@@ -1112,6 +1214,17 @@ int vhp_planner_solve_variant(vhp_ctx* ctx, int start_x, int start_y, int end_x,
 int vhp_timing(vhp_ctx* ctx, int enable) {
   if (!ctx) return VHP_ERR_ARG;
   ctx->timing = enable != 0;
+  // The ring of stamp slots for `enable` timed launches between two vhp_timing_collect calls (64 where the caller names no number);
+  // it only grows, and only while no timed launch is waiting to be collected.  Launches beyond it are timed by event pairs.
+  if (const int want = enable > 1 ? enable : 64; enable && VHP_TIMING_STAMPS && ctx->clock_khz > 0 && ctx->ring.slots() < want && ctx->ring.live() == 0) {
+    VHP_ON_DEVICE(ctx);
+    read_last_stamps(ctx);  // (the array moves: a launch that vhp_last_elapsed_ms may still be asked about is read first)
+    ctx->ring.resize(want, ctx->n_cus);
+    if (const hipError_t es = allocate_stamps(ctx); es != hipSuccess) {
+      ctx->ring.resize(0, ctx->n_cus);
+      VHP_HIP(es);
+    }
+  }
   if (enable > 1) {  // pre-create `enable` event pairs so that no launch inside a timed loop has to
     VHP_ON_DEVICE(ctx);
     while ((int)ctx->event_pool.size() < enable) {
@@ -1180,18 +1293,46 @@ int vhp_timing_collect(vhp_ctx* ctx, float* ms_out, int cap, int* n) {
   if (!ctx || !n || cap < 0 || (cap > 0 && !ms_out)) return VHP_ERR_ARG;
   VHP_ON_DEVICE(ctx);
   int k = 0, bad = 0;
-  for (auto& pr : ctx->timed_launches) {
+  // the stamped launches: the streams they went out on synchronised, then the ring's slots that are out in one copy (two where they
+  // wrap); if that fails none of them can be read
+  bool stamps_ok = true;
+  int n_stamped = 0;
+  {
+    void* synced = nullptr;
+    for (auto& t : ctx->timed_launches) {
+      if (!t.st.stamped()) continue;
+      if ((n_stamped++ == 0 || t.st.stream != synced) && hipStreamSynchronize(static_cast<hipStream_t>(t.st.stream)) != hipSuccess) stamps_ok = false;
+      synced = t.st.stream;
+    }
+    int first[2], count[2];
+    const int n_runs = n_stamped ? ctx->ring.runs(first, count) : 0;
+    for (int r = 0; r < n_runs; ++r)
+      if (copy_stamp_slots(ctx, first[r], count[r]) != hipSuccess) stamps_ok = false;
+    if (!stamps_ok) (void)hipGetLastError();
+  }
+  for (auto& t : ctx->timed_launches) {
     float ms = 0.f;
-    // a pair that cannot be read (e.g. never recorded) is dropped, not left to fail every later call
-    if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
+    bool ok;
+    if (t.st.stamped()) {
+      vhp::stamps::Time tm;
+      if (stamps_ok) tm = vhp::stamps::reduce(ctx->h_stamps.data() + ctx->ring.slot_offset(t.st.slot), t.st, ctx->clock_khz);
+      ctx->timed.read(t.st.tag, tm);  // (vhp_last_elapsed_ms reports the same number once the slot has gone back)
+      ok = tm.ok;
+      ms = tm.ms;
+    } else {
+      // a pair that cannot be read (e.g. never recorded) is dropped, not left to fail every later call
+      ok = hipEventSynchronize(t.ev.second) == hipSuccess && hipEventElapsedTime(&ms, t.ev.first, t.ev.second) == hipSuccess;
+      if (!ok) (void)hipGetLastError();
+      ctx->event_pool.push_back(t.ev);  // recycled by the next timed launches
+    }
+    if (ok) {
       if (k < cap) ms_out[k] = ms;
       ++k;
     } else {
       ++bad;
-      (void)hipGetLastError();
     }
-    ctx->event_pool.push_back(pr);  // recycled by the next timed launches
   }
+  ctx->ring.release(n_stamped);
   ctx->timed_launches.clear();
   *n = std::min(k, cap);
   if (bad) return fail(ctx, VHP_ERR_HIP, "vhp_timing_collect: " + std::to_string(bad) + " timed launch(es) could not be read");
@@ -1246,7 +1387,7 @@ int vhp_probe_stores(vhp_ctx* ctx, void* d_buf, unsigned long long bytes, float*
     }
     res[split] = (float)((double)n_tasks * 1000.0 * 1024.0 / ((double)best * 1e-3) / 1e12);
   }
-  ctx->timed = false;  // (ev0 / ev1 no longer bracket a sweep)
+  ctx->timed.nothing();  // (ev0 / ev1 no longer bracket a sweep)
   *whole_lines_TBps = res[0];
   *split_lines_TBps = res[1];
   return VHP_OK;
@@ -1322,10 +1463,16 @@ int vhp_free_output(vhp_ctx* ctx, void* d_buf) {
 
 int vhp_last_elapsed_ms(vhp_ctx* ctx, float* ms) {
   if (!ctx || !ms) return VHP_ERR_ARG;
-  if (!ctx->timed) return fail(ctx, VHP_ERR_ARG, "nothing timed yet");
+  if (ctx->timed.state == vhp::stamps::Last::kNothing) return fail(ctx, VHP_ERR_ARG, "nothing timed yet");
   VHP_ON_DEVICE(ctx);
-  VHP_HIP(hipEventSynchronize(ctx->ev1));
-  VHP_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+  if (ctx->timed.state == vhp::stamps::Last::kEvents) {
+    VHP_HIP(hipEventSynchronize(ctx->ev1));
+    VHP_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+    return VHP_OK;
+  }
+  read_last_stamps(ctx);  // (a launch that has been read -- here before, or by vhp_timing_collect -- keeps its number)
+  if (!ctx->timed.time.ok) return fail(ctx, VHP_ERR_HIP, "vhp_last_elapsed_ms: the launch's timestamps could not be read");
+  *ms = ctx->timed.time.ms;
   return VHP_OK;
 }
 
@@ -1462,7 +1609,7 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
   const int rc = vhp::planner_solve_batch(b, pm, maps ? nullptr : ctx->d_occ.get(), maps || ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream,
                                           ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg,
                                           maps ? &st : nullptr);
-  ctx->timed = true;
+  ctx->timed.events();
   if (!msg.empty()) ctx->err = msg;
   return rc;
 }

@@ -25,9 +25,18 @@ __device__ unsigned long long g_lat_strip_times[64 * 48 * 4];
 // wavefronts of a workgroup: kLatWaves sweepers and, in the band sweep, a storer beside each (16: four per SIMD, 128 vector registers)
 constexpr int kLatThreads = 64 * kLatWaves * LatWorkerT<double, false>::kRoles;
 
+// A launch's timestamp (vhp_stamps.hpp): the device's constant-rate clock and the launch's tag, one 16-byte store by the calling lane.
+__device__ __forceinline__ void write_stamp(stamps::Entry* p, unsigned long long tag) {
+  *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2((unsigned long long)wall_clock64(), tag);
+}
+
 // MULTI: the build for launches with more than one workgroup per unit (vhp_launch_plan.hpp lat_halves): its bands can read across workgroups
+// stamp_begin: where workgroup g leaves the launch's begin stamp [g] as its first act (null: the launch's pre-kernel has left it, or the
+// launch is not stamped); stamp_end: its end stamp [g], once all its wavefronts are done (null: not stamped)
 template <typename OutT, bool ODD, bool MULTI>
-__global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_sweep(LatArgs<OutT> a) {
+__global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_sweep(LatArgs<OutT> a, stamps::Entry* __restrict__ stamp_begin,
+                                                                stamps::Entry* __restrict__ stamp_end) {
+  if (stamp_begin && threadIdx.x == 0) write_stamp(stamp_begin + blockIdx.x, a.epoch);
   extern __shared__ double lds[];
   const Layout L = make_layout(kLatWaves, 1, a.m.nx, a.m.ny, kLatTilePitch);
 #ifdef VHP_DIAG_POOLPROF
@@ -39,6 +48,11 @@ __global__ void __launch_bounds__(kLatThreads, 1) vhp_lat_sweep(LatArgs<OutT> a)
   WorkerT wk;
   wk.init(a, lds, L, uniform((int)(threadIdx.x >> 6)));
   wk.run((int)blockIdx.x);
+  if (stamp_end) {  // every wavefront waits for its own stores, the barrier, then one lane reads the clock
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) write_stamp(stamp_end + blockIdx.x, a.epoch);
+  }
 #ifdef VHP_DIAG_POOLPROF
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 256 && threadIdx.x < 64 * 16) {
     unsigned long long* o = g_latprof + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 20;
@@ -133,7 +147,10 @@ __global__ void vhp_pack_diag_stack(const uint64_t* __restrict__ rows, uint64_t*
 // The units of a launch (8 per source: quadrant x {x-major, y-major}) by falling length of their march, for launches of more workgroups
 // than the chip holds at once: a counting sort by steps / 8 in one workgroup (up to 1024 x kLatOrderPerThread units).  The length of a march is what an
 // octant's time goes by (T / 16 + T / 64 windows); units of sources outside the grid go last.
-__global__ void __launch_bounds__(1024) vhp_lat_order(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order) {
+__global__ void __launch_bounds__(1024) vhp_lat_order(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order,
+                                                      stamps::Entry* __restrict__ stamp_begin, unsigned long long stamp_tag) {
+  // the launch's begin stamp, before anything else: the order kernel is part of what a launch costs
+  if (stamp_begin && threadIdx.x == 0) write_stamp(stamp_begin, stamp_tag);
   __shared__ int hist[1024], start[1024];
   const int tid = (int)threadIdx.x, n_units = n_src * kUnits;
   hist[tid] = 0;
@@ -195,6 +212,7 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
   auto ks = p.halves > 1 ? (p.odd ? vhp_lat_maps_sweep<true, true> : vhp_lat_maps_sweep<false, true>)
                          : (p.odd ? vhp_lat_maps_sweep<true, false> : vhp_lat_maps_sweep<false, false>);
   if (a.lat.map_idx && (sizeof(OutT) != 8 || pd)) return hipErrorInvalidValue;
+  if (a.d_stamps && (a.lat.map_idx || pd)) return hipErrorInvalidValue;  // (the stack's build and the planner's iteration write no stamps)
   if (!p.ok || a.pool_epoch == 0) return hipErrorInvalidValue;
   if (a.raise_lds) {
     hipError_t e = a.raise_lds(a.lat.map_idx ? reinterpret_cast<const void*>(ks) : reinterpret_cast<const void*>(k), p.lds_bytes);
@@ -250,9 +268,14 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
     }
   }
 #endif
+  // timed by the stamps its kernels write (lat_stamp_counts: the begin entry by the order kernel where there is one, else by every
+  // workgroup of the sweep) or by the events
+  const StampCounts sc = lat_stamp_counts(p, a.n_src);
+  stamps::Entry* const stamp_begin = a.d_stamps && !p.use_order_kernel ? a.d_stamps : nullptr;
+  stamps::Entry* const stamp_end = a.d_stamps ? a.d_stamps + sc.n_begin : nullptr;
   if (p.use_order_kernel) {
     // (a list of its own, not a corner of the scratch: nothing but tagged entries may ever be written where a later launch looks for tags)
-    hipLaunchKernelGGL(pool::vhp_lat_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, a.d_lat_order);
+    hipLaunchKernelGGL(pool::vhp_lat_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, a.d_lat_order, a.d_stamps, a.pool_epoch);
     g.order = a.d_lat_order;
   }
   if (a.lat.map_idx) {
@@ -261,7 +284,7 @@ hipError_t launch_lat_t(const BatchArgs& a, const PlannerDev* pd = nullptr) {
       hipLaunchKernelGGL(ks, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), p.lds_bytes, a.stream, g, st);
     }
   } else {
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), p.lds_bytes, a.stream, g);
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_src * kUnits * g.halves)), dim3(kLatThreads), p.lds_bytes, a.stream, g, stamp_begin, stamp_end);
   }
   const hipError_t e = hipGetLastError();
   if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);

@@ -180,6 +180,17 @@ inline LatPlan plan_lat(int nx, int ny, int n_src, int n_cus, bool odd, int aske
   return p;
 }
 
+// The timestamps a launch writes from inside its kernels when it is given a slot for them (vhp_stamps.hpp): one begin entry by its
+// one-workgroup pre-kernel, or one per workgroup where it has none, and one end entry per workgroup of its sweep kernel.
+struct StampCounts {
+  int n_begin, n_end;
+};
+inline StampCounts pool_stamp_counts(int n_cus) { return {1, n_cus > 0 ? n_cus : 256}; }   // (vhp_pool_order, then one workgroup per CU)
+inline StampCounts lat_stamp_counts(const LatPlan& p, int n_src) {
+  const int groups = n_src * pool::kUnits * p.halves;
+  return {p.use_order_kernel ? 1 : groups, groups};
+}
+
 inline bool lat_supported(int nx, int ny) {
   if (nx <= 0 || ny <= 0 || nx > VHP_MAX_SIDE || ny > VHP_MAX_SIDE) return false;
   // (a y-major workgroup keeps its quadrant's diagonal where an x-major one has its tiles)

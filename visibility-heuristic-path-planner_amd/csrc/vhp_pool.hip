@@ -11,8 +11,14 @@ namespace vhp {
 namespace pool {
 
 // One persistent workgroup per CU; every wavefront is a Worker (kWaves, kWavesAny: vhp_launch_plan.hpp).
+// A launch's timestamp (vhp_stamps.hpp): the device's constant-rate clock and the launch's tag, one 16-byte store by the calling lane.
+__device__ __forceinline__ void write_stamp(stamps::Entry* p, unsigned long long tag) {
+  *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2((unsigned long long)wall_clock64(), tag);
+}
+
+// stamp_end (or null: nothing is written): where workgroup g leaves the launch's end stamp [g] once all its wavefronts are done
 template <typename OutT, bool ANYW>
-__global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, int n_ctx) {
+__global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, int n_ctx, stamps::Entry* __restrict__ stamp_end) {
   extern __shared__ double lds[];
   constexpr int W = ANYW ? kWavesAny : kWaves;
   const Layout L = make_layout(W, n_ctx, a.m.nx, a.m.ny, ANYW ? kTStrideAny : kTStride);
@@ -21,6 +27,12 @@ __global__ void __launch_bounds__(64 * kWaves, 1) vhp_pool_sweep(Args<OutT> a, i
   Worker<OutT, ANYW> wk;
   wk.init(a, lds, L, uniform((int)(threadIdx.x >> 6)), (int)blockIdx.x);
   wk.run();
+  if (stamp_end) {  // (a workgroup that found no unit stamps as well: the host expects every entry)
+    // the wavefronts leave run() at different times: each waits for its own stores, the barrier, then one lane reads the clock
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) write_stamp(stamp_end + blockIdx.x, a.epoch);
+  }
 }
 
 // Launch order: one workgroup counting-sorts the 8 n_src units by the length of their march (then by cell count), longest first,
@@ -176,7 +188,10 @@ __device__ __forceinline__ void order_units_lds(const int32_t* __restrict__ src_
 __global__ void __launch_bounds__(1024) vhp_pool_order(const int32_t* __restrict__ src_xy, int n_src, int nx, int ny, int* __restrict__ order,
                                                        int* __restrict__ line_base, int* __restrict__ recs, long long capacity_blocks,
                                                        unsigned long long* __restrict__ queue, unsigned long long queue0,
-                                                       int* __restrict__ err_flag) {
+                                                       int* __restrict__ err_flag, stamps::Entry* __restrict__ stamp_begin,
+                                                       unsigned long long stamp_tag) {
+  // the launch's begin stamp, before anything else: the order kernel is part of what a launch costs
+  if (stamp_begin && threadIdx.x == 0) write_stamp(stamp_begin, stamp_tag);
   __shared__ int hist[kBuckets];
   __shared__ int wave_tot[32];
   __shared__ int blocks[kOrderLdsUnits];
@@ -226,10 +241,13 @@ hipError_t launch_pool_t(const BatchArgs& a) {
   g.n_groups = a.n_cus;
   g.static_snake = p.static_snake;
   g.static_round = p.static_round;
+  // timed by the stamps its kernels write (one begin entry, then one end entry per workgroup: pool_stamp_counts) or by the events
+  stamps::Entry* const stamp_end = a.d_stamps ? a.d_stamps + pool_stamp_counts(a.n_cus).n_begin : nullptr;
   if (a.ev_begin) (void)hipEventRecord(a.ev_begin, a.stream);  // the order pre-kernel is part of what a launch costs
   hipLaunchKernelGGL(vhp_pool_order, dim3(1), dim3(1024), 0, a.stream, a.d_src, a.n_src, a.nx, a.ny, order, line_base, recs,
-                     line_blocks_per_source(a.nx, a.ny) * a.n_src, reinterpret_cast<unsigned long long*>(a.d_queue), p.queue0, a.d_err);
-  hipLaunchKernelGGL(k, dim3((unsigned)a.n_cus), dim3(64 * p.waves), p.lds_bytes, a.stream, g, p.n_ctx);
+                     line_blocks_per_source(a.nx, a.ny) * a.n_src, reinterpret_cast<unsigned long long*>(a.d_queue), p.queue0, a.d_err,
+                     a.d_stamps, a.pool_epoch);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.n_cus), dim3(64 * p.waves), p.lds_bytes, a.stream, g, p.n_ctx, stamp_end);
   const hipError_t e = hipGetLastError();
   if (a.ev_end) (void)hipEventRecord(a.ev_end, a.stream);
   return e;
