@@ -98,6 +98,30 @@ int vhp_sync(vhp_ctx* ctx);
 int vhp_set_maps(vhp_ctx* ctx, const uint8_t* occ, int n_maps, int nx, int ny);
 /* Same, the uint8 maps already resident in device memory. */
 int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, int ny);
+/* The stack of maps as windows of the single map, cut on the device from that map's packed copies (one bit per cell read, nothing
+ * crosses to the host): n_windows maps of w x h, map k the window whose cell (0, 0) is cell (origin_xy[2k], origin_xy[2k+1]) of the
+ * map of vhp_set_map.  Window cell (i, j) is the map's cell (ox + i, oy + j) where that lies inside the grid and blocked (0) where
+ * it does not.  Every int32 origin is valid: a window may hang over any edge or lie wholly outside the grid (all blocked), and
+ * nothing is validated per window.  The stack is word for word the one vhp_set_maps builds from the same windows given as bytes, and
+ * the state is vhp_set_maps's: the call synchronises, replaces the previous stack (with its diagonal maps and the maps-batch planner's
+ * results) and leaves the single map, the planner's state, the batch planner's and "field_stride" alone.  The stack is a copy, not a
+ * view: a later vhp_set_map leaves it as it is.  Everything that runs on a stack runs on windows unchanged, IN WINDOW COORDINATES --
+ * sources, queries, paths and hit cells count from the window's cell (0, 0); adding the origin back is the caller's job.
+ * The sweep on a window equals the sweep on the whole map, bit for bit, on every window cell that is inside the grid and neither in
+ * the window's nor in the grid's first row or column (those the reference's loops never write on whatever grid they run):
+ * visibility within range r is a window of side 2 (r + 1) + 1 around the source.
+ * No single map: VHP_ERR_NO_MAP; a null pointer, n_windows < 1, w < 1 or h < 1: VHP_ERR_ARG; w or h above VHP_MAX_SIDE:
+ * VHP_ERR_TOO_LARGE; a failed allocation: VHP_ERR_HIP; on failure no stack is set.  Not timed: vhp_last_elapsed_ms keeps what it
+ * had. */
+int vhp_set_maps_windows(vhp_ctx* ctx, const int32_t* origin_xy, int n_windows, int w, int h);
+/* Same, the origins already resident in device memory; returns when the stack is on the device, as vhp_set_maps_device does. */
+int vhp_set_maps_windows_device(vhp_ctx* ctx, const int32_t* d_origin_xy, int n_windows, int w, int h);
+/* Maps first .. first + n - 1 of the current stack, however it was made, unpacked to one byte per cell (1 = free, 0 = blocked) in
+ * the layout vhp_set_maps takes: map first + k at occ_out + k*nx*ny of the stack's nx x ny.  Read from the row-packed copy; changes
+ * no state.  No stack: VHP_ERR_NO_MAP; a range outside 0 .. n_maps-1, n < 1 or a null pointer: VHP_ERR_ARG. */
+int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out);
+/* Device-resident form: asynchronous on the context stream. */
+int vhp_maps_occupancy_device(vhp_ctx* ctx, int first, int n, uint8_t* d_occ_out);
 /* Replaces computeVisibility() (solver.cpp:570-696) run on a different environment per source: field i is the sweep from
  * src_xy[2i..2i+1] on map map_idx[i] of the stack, bit for bit what vhp_set_map(that map) + vhp_sweep_batch(VHP_SWEEP_FULL,
  * dtype) gives.  Output layout, zero cells and n_src as in vhp_sweep_batch.  Always the front sweep (vhp_last_sweep_kernel

@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "vhp_planner_length_fields", "vhp_planner_length_fields_device", "vhp_planner_goal_paths", "vhp_planner_goal_paths_device",
     "vhp_raycast_batch", "vhp_raycast_batch_device", "vhp_raycast_maps_batch", "vhp_raycast_maps_batch_device",
     "vhp_line_of_sight", "vhp_line_of_sight_device",
+    "vhp_set_maps_windows", "vhp_set_maps_windows_device", "vhp_maps_occupancy", "vhp_maps_occupancy_device",
 )
 
 
@@ -98,6 +99,10 @@ def load_library():
     lib.vhp_sync.argtypes = [vp]
     lib.vhp_set_maps.argtypes = [vp, vp, i32, i32, i32]
     lib.vhp_set_maps_device.argtypes = [vp, vp, i32, i32, i32]
+    lib.vhp_set_maps_windows.argtypes = [vp, vp, i32, i32, i32]
+    lib.vhp_set_maps_windows_device.argtypes = [vp, vp, i32, i32, i32]
+    lib.vhp_maps_occupancy.argtypes = [vp, i32, i32, vp]
+    lib.vhp_maps_occupancy_device.argtypes = [vp, i32, i32, vp]
     lib.vhp_sweep_maps_batch.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_sweep_maps_batch_device.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_planner_solve.argtypes = [vp, i32, i32, i32, i32, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
@@ -236,6 +241,50 @@ class Context:
         self.n_maps = self.maps_nx = self.maps_ny = 0
         self._check(self.lib.vhp_set_maps_device(self.h, C.c_void_p(dptr), n_maps, nx, ny))
         self.n_maps, self.maps_nx, self.maps_ny = n_maps, nx, ny
+
+    def set_maps_windows(self, origins, w, h):
+        """vhp_set_maps_windows: the stack of maps as windows of the map of set_map, cut on the device.  origins int32 [n, 2] (x, y):
+        window k is the w x h cells from origins[k] on, blocked where they lie outside the grid (any int32 origin is valid).
+        Replaces the stack of set_maps; everything that runs on a stack then runs on the windows, in window coordinates (adding
+        the origin back to sources, queries, paths and hit cells is the caller's job)."""
+        org = np.ascontiguousarray(origins, np.int32).reshape(-1, 2)
+        self.n_maps = self.maps_nx = self.maps_ny = 0
+        self._check(self.lib.vhp_set_maps_windows(self.h, _ptr(org), len(org), int(w), int(h)))
+        self.n_maps, self.maps_nx, self.maps_ny = len(org), int(w), int(h)
+
+    def set_maps_windows_device(self, d_origins, n, w, h):
+        """Same, the origins (int32 [n, 2]) already in device memory (raw pointer)."""
+        self.n_maps = self.maps_nx = self.maps_ny = 0
+        self._check(self.lib.vhp_set_maps_windows_device(self.h, C.c_void_p(d_origins), int(n), int(w), int(h)))
+        self.n_maps, self.maps_nx, self.maps_ny = int(n), int(w), int(h)
+
+    def maps_occupancy(self, first=0, n=None):
+        """vhp_maps_occupancy: maps first .. first + n - 1 of the stack (default: all from `first`) as uint8 [n, maps_ny, maps_nx],
+        1 = free -- what set_maps would take."""
+        n = self.n_maps - int(first) if n is None else int(n)
+        out = np.empty((max(n, 0), self.maps_ny, self.maps_nx), np.uint8)
+        self._check(self.lib.vhp_maps_occupancy(self.h, int(first), n, _ptr(out)))
+        return out
+
+    def maps_occupancy_device(self, d_out, first=0, n=None):
+        """Device-resident, asynchronous on the context stream.  d_out is a raw device pointer to n * maps_ny * maps_nx bytes."""
+        n = self.n_maps - int(first) if n is None else int(n)
+        self._check(self.lib.vhp_maps_occupancy_device(self.h, int(first), n, C.c_void_p(d_out)))
+
+    def sweep_windows(self, sources, radius, dtype=F64):
+        """Range-limited sweeps around many sources of the map of set_map: sets windows of side 2 * radius + 1 with origin
+        source - radius (set_maps_windows: this REPLACES the stack of maps) and returns sweep_maps_batch of the local source
+        (radius, radius) on window i -- fields [n, 2 * radius + 1, 2 * radius + 1] in window coordinates, field i's cell (a, b) being
+        the map's cell sources[i] - radius + (a, b).  Away from its first row and column -- the reference's zeros on whatever grid
+        it sweeps (unless the source lies on them), so ask for radius + 1 -- and from the grid's first row and column, every cell
+        inside the grid holds, bit for bit, what sweep_batch on the whole map holds there; cells outside the grid are blocked."""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+        r = int(radius)
+        if r < 0:
+            raise ValueError("sweep_windows: radius must be >= 0, got %d" % r)
+        side = 2 * r + 1
+        self.set_maps_windows((src.astype(np.int64) - r).astype(np.int32), side, side)
+        return self.sweep_maps_batch(np.full((len(src), 2), r, np.int32), np.arange(len(src), dtype=np.int32), dtype)
 
     def sweep_maps_batch(self, sources, map_index, dtype=F64):
         """Host-buffer form.  sources int32 [n, 2] (x, y), map_index int32 [n] (the map of each source) -> fields [n, ny, nx]."""

@@ -524,6 +524,41 @@ int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, boo
   });
 }
 
+// The stack of vhp_set_maps_windows: n_win windows of w x h of the single map, cut from its packed copies at the origins at src (host
+// or device) -- one thread per word, one launch per copy.
+int build_windows(vhp_ctx* ctx, const int32_t* src, int n_win, int w, int h, bool from_device) {
+  vhp::DevBuf<int32_t> staged;  // the host origins' device copy, for the cut only
+  const int32_t* d_origin = src;
+  if (!from_device) {
+    VHP_HIP(staged.grow((size_t)n_win * 2 * sizeof(int32_t)));
+    VHP_HIP(hipMemcpyAsync(staged.get(), src, (size_t)n_win * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    d_origin = staged.get();
+  }
+  const vhp::PackedMaps& s = ctx->map;
+  vhp::PackedMaps& m = ctx->maps;
+  return build_packed(ctx, m, n_win, w, h, [&](int wpr, int wpc, unsigned, unsigned) -> int {
+    const unsigned gy = (unsigned)std::min(n_win, 65535);  // (the kernels step through more windows than that)
+    const unsigned row_blocks = (unsigned)(((long long)(wpr - 2) * h + 255) / 256), col_blocks = (unsigned)(((long long)(wpc - 2) * w + 255) / 256);
+    hipLaunchKernelGGL(vhp::vhp_cut_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, s.rows.get(), s.nx, s.ny, s.wpr, d_origin,
+                       m.rows.get(), n_win, w, h, wpr);
+    VHP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(vhp::vhp_cut_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, s.cols.get(), s.nx, s.ny, s.wpc, d_origin,
+                       m.cols.get(), n_win, w, h, wpc);
+    VHP_HIP(hipGetLastError());
+    return VHP_OK;
+  });
+}
+
+// Maps first .. first + n - 1 of the stack as bytes at d_out (vhp_maps_occupancy_device: checked by the caller)
+int unpack_maps(vhp_ctx* ctx, int first, int n, uint8_t* d_out) {
+  const vhp::PackedMaps& m = ctx->maps;
+  const unsigned blocks = (unsigned)(((long long)m.nx * m.ny + 255) / 256);
+  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3(blocks, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream,
+                     m.rows.get() + (size_t)first * m.ny * m.wpr, d_out, n, m.nx, m.ny, m.wpr);
+  VHP_HIP(hipGetLastError());
+  return VHP_OK;
+}
+
 // G of a batch solve (vhp_planner_solve_batch): the largest of 32, 16, 8, 4, 2 for which a launch of G sources takes the latency sweep
 // and G queries' state fits in a quarter of the free device memory, else 1 -- capped by "planner_batch_group" --; 0 where even one
 // source does not take the latency sweep (the queries then run one by one on the front sweep).
@@ -962,6 +997,56 @@ static int set_maps_common(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx,
 
 int vhp_set_maps(vhp_ctx* ctx, const uint8_t* occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, occ, n_maps, nx, ny, false); }
 int vhp_set_maps_device(vhp_ctx* ctx, const uint8_t* d_occ, int n_maps, int nx, int ny) { return set_maps_common(ctx, d_occ, n_maps, nx, ny, true); }
+
+static int set_maps_windows_common(vhp_ctx* ctx, const int32_t* origin_xy, int n_windows, int w, int h, bool from_device) {
+  const std::string who = from_device ? "vhp_set_maps_windows_device" : "vhp_set_maps_windows";
+  if (!ctx || !origin_xy || n_windows < 1 || w <= 0 || h <= 0) return fail(ctx, VHP_ERR_ARG, who + ": bad argument");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, who + ": no map set");
+  if (w > VHP_MAX_SIDE || h > VHP_MAX_SIDE) return fail(ctx, VHP_ERR_TOO_LARGE, who + ": window side exceeds VHP_MAX_SIDE");
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  free_maps(ctx);  // (as vhp_set_maps: the single map, the planner's state and "field_stride" stay)
+  const int rc = build_windows(ctx, origin_xy, n_windows, w, h, from_device);
+  if (rc != VHP_OK) free_maps(ctx);
+  return rc;
+}
+
+int vhp_set_maps_windows(vhp_ctx* ctx, const int32_t* origin_xy, int n_windows, int w, int h) {
+  return set_maps_windows_common(ctx, origin_xy, n_windows, w, h, false);
+}
+int vhp_set_maps_windows_device(vhp_ctx* ctx, const int32_t* d_origin_xy, int n_windows, int w, int h) {
+  return set_maps_windows_common(ctx, d_origin_xy, n_windows, w, h, true);
+}
+
+static int maps_occupancy_check(vhp_ctx* ctx, const char* who, int first, int n, const uint8_t* out) {
+  if (!ctx || !out || n < 1) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
+  if (!ctx->maps.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no maps set");
+  if (first < 0 || first >= ctx->maps.n || n > ctx->maps.n - first) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": maps outside the stack");
+  return VHP_OK;
+}
+
+int vhp_maps_occupancy_device(vhp_ctx* ctx, int first, int n, uint8_t* d_occ_out) {
+  if (const int rc = maps_occupancy_check(ctx, "vhp_maps_occupancy_device", first, n, d_occ_out); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  return unpack_maps(ctx, first, n, d_occ_out);
+}
+
+int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out) {
+  if (const int rc = maps_occupancy_check(ctx, "vhp_maps_occupancy", first, n, occ_out); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  // slices of at most ~1 GiB through the context's scratch, as the host-buffer sweeps' fields (stage_slices)
+  const size_t cells = (size_t)ctx->maps.nx * ctx->maps.ny;
+  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / cells));
+  const hipError_t e = ctx->d_out.grow((size_t)slice * cells);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_maps_occupancy: scratch: ") + hipGetErrorString(e));
+  for (int k0 = 0; k0 < n; k0 += slice) {
+    const int nk = std::min(slice, n - k0);
+    if (const int rc = unpack_maps(ctx, first + k0, nk, static_cast<uint8_t*>(ctx->d_out.get())); rc != VHP_OK) return rc;
+    VHP_HIP(hipMemcpyAsync(occ_out + (size_t)k0 * cells, ctx->d_out.get(), (size_t)nk * cells, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return VHP_OK;
+}
 
 static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out,
                                    const LaunchOpts& o) {

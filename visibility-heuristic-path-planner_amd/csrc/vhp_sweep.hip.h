@@ -56,6 +56,7 @@
 
 #include "vhp_devbuf.hip.h"
 #include "vhp_diag.h"
+#include "vhp_window.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -1382,6 +1383,44 @@ __global__ void vhp_pack_cols_stack(const uint8_t* __restrict__ occ, uint64_t* _
     const uint64_t b = __ballot(f);
     if (lane == 0) cols[(size_t)k * nx * wpc + (size_t)x * wpc + 1 + w] = b;
   }
+}
+
+// A stack of n_win windows of w x h cut from the packed copies of one nx x ny map (vhp_set_maps_windows): window k starts at the map's
+// cell (origin_xy[2k], origin_xy[2k+1]), any int32.  One thread per data word (vhp_window.hpp window_word), the pads left to the
+// caller's memset; blockIdx.y picks the window as above.  Neighbouring threads read neighbouring words of one source line.
+__global__ void vhp_cut_rows_stack(const uint64_t* __restrict__ src_rows, int nx, int ny, int src_wpr, const int32_t* __restrict__ origin_xy,
+                                   uint64_t* __restrict__ rows, int n_win, int w, int h, int wpr) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int words = wpr - 2;
+  if (t >= words * h) return;
+  const int j = t / words, k = t - j * words;
+  for (int i = blockIdx.y; i < n_win; i += gridDim.y) {
+    const long long y = window_line(origin_xy[2 * i + 1], j, ny);
+    rows[(size_t)i * h * wpr + (size_t)j * wpr + 1 + k] = window_word(y < 0 ? nullptr : src_rows + (size_t)y * src_wpr, nx, origin_xy[2 * i], w, k);
+  }
+}
+
+// ... and the column-packed copy: the same cut along y of the map's columns
+__global__ void vhp_cut_cols_stack(const uint64_t* __restrict__ src_cols, int nx, int ny, int src_wpc, const int32_t* __restrict__ origin_xy,
+                                   uint64_t* __restrict__ cols, int n_win, int w, int h, int wpc) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int words = wpc - 2;
+  if (t >= words * w) return;
+  const int j = t / words, k = t - j * words;
+  for (int i = blockIdx.y; i < n_win; i += gridDim.y) {
+    const long long x = window_line(origin_xy[2 * i], j, nx);
+    cols[(size_t)i * w * wpc + (size_t)j * wpc + 1 + k] = window_word(x < 0 ? nullptr : src_cols + (size_t)x * src_wpc, ny, origin_xy[2 * i + 1], h, k);
+  }
+}
+
+// Maps first .. first + n - 1 of a stack back to one byte per cell (1 = free), from the row-packed copy (vhp_maps_occupancy): one
+// thread per cell of a map, blockIdx.y picks the map as above; rows points at map `first`.
+__global__ void vhp_unpack_rows_stack(const uint64_t* __restrict__ rows, uint8_t* __restrict__ occ, int n, int nx, int ny, int wpr) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nx * ny) return;
+  const int y = c / nx, x = c - y * nx;
+  for (int k = blockIdx.y; k < n; k += gridDim.y)
+    occ[(size_t)k * nx * ny + c] = (rows[(size_t)k * ny * wpr + (size_t)y * wpr + 1 + (x >> 6)] >> (x & 63)) & 1;
 }
 
 }  // namespace vhp
