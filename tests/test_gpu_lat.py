@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import maps
+from hard_maps import salt_walled as _walled
 
 pytestmark = pytest.mark.gpu
 
@@ -101,15 +102,6 @@ def test_lat_kernel_bad_source_is_reported(vhp):
     src[23] = (3, -1)
     with pytest.raises(Exception):
         c.sweep_batch(src)
-
-
-def _walled(nx, ny, seed, density):
-    rng = np.random.RandomState(seed)
-    occ = (rng.rand(ny, nx) >= density).astype(np.uint8)
-    for k in range(3):
-        occ[rng.randint(0, ny), :] = 0
-        occ[:, rng.randint(0, nx)] = 0
-    return occ
 
 
 @pytest.mark.parametrize("nx,ny,density", [(200, 163, 0.5), (328, 300, 0.2), (640, 603, 0.08), (1104, 72, 0.3), (72, 1100, 0.3), (130, 131, 0.95),
