@@ -29,8 +29,10 @@ static_assert(kTreeErrEndOob == VHP_ERR_END_OOB, "vhp_tree.hpp restates vhp.h's 
 // LDS staging bound of vhp_tree_fields: tables of up to 1024 pivots, 20 bytes each = 20 KiB per workgroup.  By the arithmetic, eight
 // workgroups of 256 threads -- the CU's full 32 wavefronts -- then hold 160 KiB, all of a CU's LDS and no more, so the static
 // allocation should not lower the resident wavefronts.  NOT MEASURED: neither that residency, nor whether staging beats reading a
-// table of a few KB through L2.  Planner solves here end after 3-250 pivots; a larger table (a fast speculative solve with a huge
-// max_iter) is read through L2.
+// table of a few KB through L2.  Most planner solves end after 3-250 pivots; a table of 1024 pivots or more (a long solve on a
+// cluttered map, a fast speculative solve with a large max_iter) is read through L2.  Both branches are tested against the oracle at
+// every cell: staged tables of up to 984 entries, tables of 1038 to 2834 entries through L2, and launches that mix the two under the
+// stride max_nb + 1 (tests/test_gpu_long_solves.py).
 constexpr uint32_t kTreeLdsPivots = 1024;
 constexpr int kTreeThreads = 256;
 constexpr int kTreeCellsPerThread = 16;                          // four groups of four consecutive cells
