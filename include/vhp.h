@@ -122,6 +122,49 @@ int vhp_set_maps_windows_device(vhp_ctx* ctx, const int32_t* d_origin_xy, int n_
 int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out);
 /* Device-resident form: asynchronous on the context stream. */
 int vhp_maps_occupancy_device(vhp_ctx* ctx, int first, int n, uint8_t* d_occ_out);
+
+/* Obstacles grown by a robot's footprint, on the device (the configuration-space map: everything here plans for a point).  A
+ * footprint is a set of integer offsets (dx, dy) picked by `shape` and one integer p >= 0:
+ *   VHP_FOOT_DISC     dx*dx + dy*dy <= p        (p is the SQUARED radius in cells: every digital disc is reachable, no square root)
+ *   VHP_FOOT_SQUARE   max(|dx|, |dy|) <= p
+ *   VHP_FOOT_DIAMOND  |dx| + |dy| <= p
+ * Its reach, the largest |dx| -- isqrt(p), p, p --, is at most VHP_MAX_INFLATE cells.  Cell (x, y) of the inflated map is blocked
+ * exactly when some cell (x + dx, y + dy), (dx, dy) in the footprint, is blocked in the input.  Cells outside the grid count as FREE
+ * (a map's edge is no wall) unless flags has VHP_INFLATE_BORDER, which makes them blocked: every cell within the footprint of the
+ * edge is then blocked too.  p = 0 is the identity footprint: the same map, and the same changes of state.
+ *
+ * vhp_inflate_map replaces the single map by its inflation, computed from the row-packed copy.  Afterwards the context is in the
+ * state vhp_set_map_device of the inflated bytes would leave: the uint8 map, both packed copies, the diagonal maps where the latency
+ * sweep takes the grid, no host copy of the map, "field_stride" reset to 0, the results of the plain, speculative and batch solves
+ * dropped; the stack of maps and its solves untouched.  Every later call on the single map is bit for bit what it is after
+ * vhp_set_map of the inflated map.  Synchronous, as vhp_set_map is; not timed: vhp_last_elapsed_ms keeps what it had.
+ * No map: VHP_ERR_NO_MAP; an unknown shape, p < 0, a reach above VHP_MAX_INFLATE or a flag bit other than VHP_INFLATE_BORDER:
+ * VHP_ERR_ARG; a refused call changes nothing.  A failed HIP call: VHP_ERR_HIP, with the map as it was if the inflation itself
+ * failed and no map set if the rebuild after it did (as a failed vhp_set_map leaves none).
+ *
+ * vhp_inflate_maps does the same to maps first .. first + n - 1 of the stack, whether it came from bytes or from windows; the
+ * other maps stay word for word.  Both packed copies of the range are inflated into scratch and copied back, and the stack is then in
+ * the state vhp_set_maps_device of the resulting bytes would leave: its lazily built diagonal maps and the maps batch's results are
+ * gone, the single map, its solves and "field_stride" stay.  Synchronous, not timed.  No stack (a single map is none):
+ * VHP_ERR_NO_MAP; a range outside 0 .. n_maps-1 or n < 1 (as vhp_maps_occupancy) or a bad footprint or flag (as above): VHP_ERR_ARG,
+ * nothing changed.  A failed HIP call: VHP_ERR_HIP and the stack is EMPTY (no stack set), never a mix of old and new maps.
+ *
+ * How the calls compose.  Inflate the single map BEFORE cutting windows from it (vhp_set_maps_windows): a window of the inflated map
+ * also holds the growth of obstacles that lie just outside the window, which inflating a cut window cannot know -- it sees the
+ * window's cells outside the grid as the blocked cells the cut made them, and nothing beyond the window.  A fleet of K robot sizes on
+ * one map: vhp_set_maps_windows with K origins (0, 0) and w, h = nx, ny (K device copies of the map), vhp_inflate_maps(k, 1, ...) per
+ * size, then vhp_planner_solve_maps_batch with map_idx[q] = the class of query q's robot. */
+typedef enum vhp_footprint { VHP_FOOT_DISC = 0, VHP_FOOT_SQUARE = 1, VHP_FOOT_DIAMOND = 2 } vhp_footprint;
+#define VHP_MAX_INFLATE 64
+#define VHP_INFLATE_BORDER 1
+int vhp_inflate_map(vhp_ctx* ctx, int shape, int p, int flags);
+int vhp_inflate_maps(vhp_ctx* ctx, int first, int n, int shape, int p, int flags);
+/* The single map unpacked to one byte per cell (1 = free, 0 = blocked: normalised, whatever non-zero bytes vhp_set_map was given),
+ * nx*ny bytes in the layout vhp_set_map takes.  Read from the row-packed copy; changes no state.  What shows an inflated map.
+ * No map: VHP_ERR_NO_MAP; a null pointer: VHP_ERR_ARG. */
+int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out);
+/* Device-resident form: asynchronous on the context stream. */
+int vhp_map_occupancy_device(vhp_ctx* ctx, uint8_t* d_occ_out);
 /* Replaces computeVisibility() (solver.cpp:570-696) run on a different environment per source: field i is the sweep from
  * src_xy[2i..2i+1] on map map_idx[i] of the stack, bit for bit what vhp_set_map(that map) + vhp_sweep_batch(VHP_SWEEP_FULL,
  * dtype) gives.  Output layout, zero cells and n_src as in vhp_sweep_batch.  Always the front sweep (vhp_last_sweep_kernel

@@ -57,7 +57,44 @@ ABI_SYMBOLS = (
     "vhp_raycast_batch", "vhp_raycast_batch_device", "vhp_raycast_maps_batch", "vhp_raycast_maps_batch_device",
     "vhp_line_of_sight", "vhp_line_of_sight_device",
     "vhp_set_maps_windows", "vhp_set_maps_windows_device", "vhp_maps_occupancy", "vhp_maps_occupancy_device",
+    "vhp_inflate_map", "vhp_inflate_maps", "vhp_map_occupancy", "vhp_map_occupancy_device",
 )
+
+FOOT_DISC, FOOT_SQUARE, FOOT_DIAMOND = 0, 1, 2   # vhp_footprint
+MAX_INFLATE = 64        # VHP_MAX_INFLATE: the largest reach of a footprint, in cells
+INFLATE_BORDER = 1      # VHP_INFLATE_BORDER: cells outside the grid count as blocked
+_FOOT_SHAPES = {"disc": FOOT_DISC, "square": FOOT_SQUARE, "diamond": FOOT_DIAMOND}
+
+
+def footprint(radius=None, shape="disc", p=None):
+    """(shape, p) of vhp_inflate_map from a footprint given the Python way: shape "disc", "square" or "diamond" and exactly one of
+    `radius` (in cells) and `p` (the C ABI's parameter).  A disc's p is its squared radius, floor(radius^2) computed exactly from the
+    value given (an int, a float -- every float is a ratio of integers --, a Fraction or a Decimal), so a fractional radius picks the
+    digital disc it means: 2.9 -> 8, 3 -> 9.  The other shapes take an integer radius, which is their p.  ValueError for anything
+    else; the reach itself (at most MAX_INFLATE) is the library's to check."""
+    from fractions import Fraction
+    if shape not in _FOOT_SHAPES:
+        raise ValueError("footprint: shape must be one of %s, got %r" % (", ".join(sorted(_FOOT_SHAPES)), shape))
+    if (radius is None) == (p is None):
+        raise ValueError("footprint: give exactly one of radius and p")
+    if p is not None:
+        if isinstance(p, bool) or int(p) != p or not 0 <= p < 2 ** 31:
+            raise ValueError("footprint: p must be an integer >= 0 (and a C int), got %r" % (p,))
+        return _FOOT_SHAPES[shape], int(p)
+    try:
+        r = Fraction(radius)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("footprint: radius must be a finite number, got %r" % (radius,)) from None
+    if r < 0:
+        raise ValueError("footprint: radius must be >= 0, got %r" % (radius,))
+    if r > 2 ** 15:   # (far past MAX_INFLATE; keeps p inside a C int)
+        raise ValueError("footprint: radius %r is beyond any footprint" % (radius,))
+    if shape == "disc":
+        r2 = r * r
+        return FOOT_DISC, r2.numerator // r2.denominator
+    if r.denominator != 1:
+        raise ValueError("footprint: a %s takes an integer radius, got %r" % (shape, radius))
+    return _FOOT_SHAPES[shape], int(r)
 
 
 class VhpError(RuntimeError):
@@ -103,6 +140,10 @@ def load_library():
     lib.vhp_set_maps_windows_device.argtypes = [vp, vp, i32, i32, i32]
     lib.vhp_maps_occupancy.argtypes = [vp, i32, i32, vp]
     lib.vhp_maps_occupancy_device.argtypes = [vp, i32, i32, vp]
+    lib.vhp_inflate_map.argtypes = [vp, i32, i32, i32]
+    lib.vhp_inflate_maps.argtypes = [vp, i32, i32, i32, i32, i32]
+    lib.vhp_map_occupancy.argtypes = [vp, vp]
+    lib.vhp_map_occupancy_device.argtypes = [vp, vp]
     lib.vhp_sweep_maps_batch.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_sweep_maps_batch_device.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_planner_solve.argtypes = [vp, i32, i32, i32, i32, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
@@ -270,6 +311,40 @@ class Context:
         """Device-resident, asynchronous on the context stream.  d_out is a raw device pointer to n * maps_ny * maps_nx bytes."""
         n = self.n_maps - int(first) if n is None else int(n)
         self._check(self.lib.vhp_maps_occupancy_device(self.h, int(first), n, C.c_void_p(d_out)))
+
+    def inflate_map(self, radius=None, shape="disc", p=None, border=False):
+        """vhp_inflate_map: the map of set_map replaced by its inflation by a robot's footprint, on the device -- a cell is blocked
+        afterwards exactly when the footprint around it touches a blocked cell.  The footprint as in `footprint` (one of radius and
+        p; a reach of at most MAX_INFLATE cells); cells outside the grid are free, or blocked with border=True.  The context is then
+        as after set_map_device of the inflated map (field_stride 0, the solves on the single map dropped, the stack untouched).
+        Inflate BEFORE cutting windows (set_maps_windows): a window of the inflated map knows the obstacles just outside it, an
+        inflated window does not."""
+        s, p = footprint(radius, shape, p)
+        self._check(self.lib.vhp_inflate_map(self.h, s, p, INFLATE_BORDER if border else 0))
+        self.field_stride = 0
+
+    def inflate_maps(self, first=0, n=None, radius=None, shape="disc", p=None, border=False):
+        """vhp_inflate_maps: the same for maps first .. first + n - 1 of the stack (default: all from `first`), the others left as
+        they are; the results of a maps batch are dropped.  K robot sizes on one map: set_maps_windows([(0, 0)] * K, nx, ny),
+        inflate_maps(k, 1, ...) per size, planner_solve_maps_batch with map_index[q] the class of query q's robot."""
+        s, p = footprint(radius, shape, p)
+        n = self.n_maps - int(first) if n is None else int(n)
+        try:
+            self._check(self.lib.vhp_inflate_maps(self.h, int(first), n, s, p, INFLATE_BORDER if border else 0))
+        except VhpError as e:
+            if e.code == VHP_ERR_HIP:   # (the library leaves no stack behind a failed HIP call)
+                self.n_maps = self.maps_nx = self.maps_ny = 0
+            raise
+
+    def map_occupancy(self):
+        """vhp_map_occupancy: the map of set_map as uint8 [ny, nx], normalised to 1 = free, 0 = blocked -- what shows an inflated map."""
+        out = np.empty((self.ny, self.nx), np.uint8)
+        self._check(self.lib.vhp_map_occupancy(self.h, _ptr(out)))
+        return out
+
+    def map_occupancy_device(self, d_out):
+        """Device-resident, asynchronous on the context stream.  d_out is a raw device pointer to ny * nx bytes."""
+        self._check(self.lib.vhp_map_occupancy_device(self.h, C.c_void_p(d_out)))
 
     def sweep_windows(self, sources, radius, dtype=F64):
         """Range-limited sweeps around many sources of the map of set_map: sets windows of side 2 * radius + 1 with origin

@@ -94,6 +94,7 @@ struct vhp_ctx {
   // built by the first planner batch on the stack that takes the latency sweep (vhp_planner_solve_maps_batch) and kept until the stack goes
   vhp::PackedMaps maps;
   vhp::DevBuf<int32_t> d_map_idx;   // host-buffer form's slice of map indices (grow-only)
+  vhp::DevBuf<uint64_t> d_inflate;  // vhp_inflate_map / vhp_inflate_maps: the inflated packed copies before they replace the old ones (grow-only)
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
   vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
@@ -556,6 +557,24 @@ int unpack_maps(vhp_ctx* ctx, int first, int n, uint8_t* d_out) {
   hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3(blocks, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream,
                      m.rows.get() + (size_t)first * m.ny * m.wpr, d_out, n, m.nx, m.ny, m.wpr);
   VHP_HIP(hipGetLastError());
+  return VHP_OK;
+}
+
+// One packed copy of n maps -- `lines` lines of `cells` cells, wpl words each, from src on -- inflated by the footprint t to dst
+// (vhp_inflate_stack: one thread per data word, the pads of dst the caller's).
+int inflate_copy(vhp_ctx* ctx, const uint64_t* src, uint64_t* dst, int n, int lines, int cells, int wpl, const vhp::InflateTable& t, int flags) {
+  const unsigned blocks = (unsigned)(((long long)(wpl - 2) * lines + 255) / 256);
+  hipLaunchKernelGGL(vhp::vhp_inflate_stack, dim3(blocks, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream, src, dst, n, lines, cells, wpl, t,
+                     flags & VHP_INFLATE_BORDER);
+  VHP_HIP(hipGetLastError());
+  return VHP_OK;
+}
+
+// The footprint of vhp_inflate_map / vhp_inflate_maps, or why not
+int inflate_footprint(vhp_ctx* ctx, const char* who, int shape, int p, int flags, vhp::InflateTable* t) {
+  static_assert(vhp::kMaxInflate == VHP_MAX_INFLATE, "vhp_inflate.hpp and vhp.h disagree on the largest reach");
+  if ((flags & ~VHP_INFLATE_BORDER) != 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": unknown flag");
+  if (!vhp::inflate_table(shape, p, t)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": unknown shape, p < 0 or a reach above VHP_MAX_INFLATE");
   return VHP_OK;
 }
 
@@ -1045,6 +1064,93 @@ int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out) {
     VHP_HIP(hipMemcpyAsync(occ_out + (size_t)k0 * cells, ctx->d_out.get(), (size_t)nk * cells, hipMemcpyDeviceToHost, ctx->stream));
     VHP_HIP(hipStreamSynchronize(ctx->stream));
   }
+  return VHP_OK;
+}
+
+int vhp_inflate_map(vhp_ctx* ctx, int shape, int p, int flags) {
+  if (!ctx) return VHP_ERR_ARG;
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_inflate_map: no map set");
+  vhp::InflateTable t;
+  if (const int rc = inflate_footprint(ctx, "vhp_inflate_map", shape, p, flags, &t); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  // the inflated rows into scratch (their data words: all the unpacking reads), then vhp_set_map_device's route from their bytes
+  const int nx = ctx->map.nx, ny = ctx->map.ny, wpr = ctx->map.wpr;
+  VHP_HIP(ctx->d_inflate.grow((size_t)ny * wpr * 8));
+  if (const int rc = inflate_copy(ctx, ctx->map.rows.get(), ctx->d_inflate.get(), 1, ny, nx, wpr, t, flags); rc != VHP_OK) return rc;
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  free_map(ctx);
+  ctx->opt_field_stride = 0;
+  VHP_HIP(ctx->d_occ.grow((size_t)nx * ny));
+  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3((unsigned)(((long long)nx * ny + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->d_inflate.get(),
+                     ctx->d_occ.get(), 1, nx, ny, wpr);
+  int rc = VHP_OK;
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) rc = fail(ctx, VHP_ERR_HIP, std::string("vhp_inflate_map: unpack: ") + hipGetErrorString(e));
+  if (rc == VHP_OK) rc = finish_set_map(ctx, nx, ny);
+  if (rc != VHP_OK) free_map(ctx);  // (as a failed vhp_set_map: no map, not half of one)
+  return rc;
+}
+
+int vhp_inflate_maps(vhp_ctx* ctx, int first, int n, int shape, int p, int flags) {
+  if (!ctx) return VHP_ERR_ARG;
+  vhp::PackedMaps& m = ctx->maps;
+  if (!m.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_inflate_maps: no maps set");
+  if (n < 1 || first < 0 || first >= m.n || n > m.n - first) return fail(ctx, VHP_ERR_ARG, "vhp_inflate_maps: maps outside the stack");
+  vhp::InflateTable t;
+  if (const int rc = inflate_footprint(ctx, "vhp_inflate_maps", shape, p, flags, &t); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  // both copies of the range into scratch -- zeroed first: the pads --, then over the range; anything that fails empties the stack
+  const size_t row_words = (size_t)n * m.ny * m.wpr, col_words = (size_t)n * m.nx * m.wpc;
+  uint64_t* const rows = m.rows.get() + (size_t)first * m.ny * m.wpr;
+  uint64_t* const cols = m.cols.get() + (size_t)first * m.nx * m.wpc;
+  const int rc = [&]() -> int {
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+    VHP_HIP(ctx->d_inflate.grow((row_words + col_words) * 8));
+    uint64_t* const new_rows = ctx->d_inflate.get();
+    uint64_t* const new_cols = new_rows + row_words;
+    VHP_HIP(hipMemsetAsync(new_rows, 0, (row_words + col_words) * 8, ctx->stream));
+    if (const int r = inflate_copy(ctx, rows, new_rows, n, m.ny, m.nx, m.wpr, t, flags); r != VHP_OK) return r;
+    if (const int r = inflate_copy(ctx, cols, new_cols, n, m.nx, m.ny, m.wpc, t, flags); r != VHP_OK) return r;
+    VHP_HIP(hipMemcpyAsync(rows, new_rows, row_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    VHP_HIP(hipMemcpyAsync(cols, new_cols, col_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+    return VHP_OK;
+  }();
+  if (rc != VHP_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    free_maps(ctx);
+    return rc;
+  }
+  m.dmap.reset();  // (built again by the next planner batch on the stack that takes the latency sweep)
+  vhp::batch_free(ctx->maps_batch);
+  return VHP_OK;
+}
+
+static int unpack_map(vhp_ctx* ctx, uint8_t* d_out) {
+  const vhp::PackedMaps& m = ctx->map;
+  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3((unsigned)(((long long)m.nx * m.ny + 255) / 256), 1), dim3(256), 0, ctx->stream, m.rows.get(), d_out,
+                     1, m.nx, m.ny, m.wpr);
+  VHP_HIP(hipGetLastError());
+  return VHP_OK;
+}
+
+int vhp_map_occupancy_device(vhp_ctx* ctx, uint8_t* d_occ_out) {
+  if (!ctx || !d_occ_out) return fail(ctx, VHP_ERR_ARG, "vhp_map_occupancy_device: bad argument");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_map_occupancy_device: no map set");
+  VHP_ON_DEVICE(ctx);
+  return unpack_map(ctx, d_occ_out);
+}
+
+int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out) {
+  if (!ctx || !occ_out) return fail(ctx, VHP_ERR_ARG, "vhp_map_occupancy: bad argument");
+  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_map_occupancy: no map set");
+  VHP_ON_DEVICE(ctx);
+  const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
+  const hipError_t e = ctx->d_out.grow(cells);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_map_occupancy: scratch: ") + hipGetErrorString(e));
+  if (const int rc = unpack_map(ctx, static_cast<uint8_t*>(ctx->d_out.get())); rc != VHP_OK) return rc;
+  VHP_HIP(hipMemcpyAsync(occ_out, ctx->d_out.get(), cells, hipMemcpyDeviceToHost, ctx->stream));
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
   return VHP_OK;
 }
 

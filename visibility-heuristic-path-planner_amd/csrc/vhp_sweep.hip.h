@@ -56,6 +56,7 @@
 
 #include "vhp_devbuf.hip.h"
 #include "vhp_diag.h"
+#include "vhp_inflate.hpp"
 #include "vhp_window.hpp"
 
 #include <algorithm>
@@ -1421,6 +1422,24 @@ __global__ void vhp_unpack_rows_stack(const uint64_t* __restrict__ rows, uint8_t
   const int y = c / nx, x = c - y * nx;
   for (int k = blockIdx.y; k < n; k += gridDim.y)
     occ[(size_t)k * nx * ny + c] = (rows[(size_t)k * ny * wpr + (size_t)y * wpr + 1 + (x >> 6)] >> (x & 63)) & 1;
+}
+
+// One packed copy of n_maps maps with their obstacles grown by a footprint (vhp_inflate_map, vhp_inflate_maps): map i's `lines` lines
+// of `cells` cells, wpl words each, at src + i * lines * wpl, inflated to the same place of dst -- never src itself: a word is read by
+// up to 129 lines' threads.  The row-packed copy takes (lines, cells, wpl) = (ny, nx, wpr), the column-packed one (nx, ny, wpc): the
+// footprints are symmetric under x <-> y (vhp_inflate.hpp), so one kernel serves both.  One thread per data word, neighbouring
+// threads on neighbouring words of one line, the pads left to the caller; blockIdx.y picks the map as above.  The table is uniform
+// and indexed by the uniform loop counter: it stays in the kernel arguments.
+__global__ void __launch_bounds__(256) vhp_inflate_stack(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, int n_maps, int lines, int cells,
+                                                         int wpl, InflateTable tab, int border) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int words = wpl - 2;
+  if (t >= words * lines) return;
+  const int j = t / words, k = t - j * words;
+  for (int i = blockIdx.y; i < n_maps; i += gridDim.y) {
+    const size_t at = (size_t)i * lines * wpl;
+    dst[at + (size_t)j * wpl + 1 + k] = inflate_word(src + at, wpl, lines, cells, tab, border != 0, j, k);
+  }
 }
 
 }  // namespace vhp
