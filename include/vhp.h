@@ -165,6 +165,32 @@ int vhp_inflate_maps(vhp_ctx* ctx, int first, int n, int shape, int p, int flags
 int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out);
 /* Device-resident form: asynchronous on the context stream. */
 int vhp_map_occupancy_device(vhp_ctx* ctx, uint8_t* d_occ_out);
+
+/* The clearance field: for every cell the distance to the nearest obstacle, in the terms of the footprints above -- the smallest p at
+ * which vhp_inflate_map(shape, p, flags) would block the cell.  With the metric m(dx, dy) of `shape`,
+ *   VHP_FOOT_DISC     dx*dx + dy*dy             (the SQUARED distance in cells)
+ *   VHP_FOOT_SQUARE   max(|dx|, |dy|)
+ *   VHP_FOOT_DIAMOND  |dx| + |dy|
+ * c(x, y) is the minimum of m(dx, dy) over all (dx, dy) for which cell (x + dx, y + dy) is blocked; with VHP_INFLATE_BORDER in `flags`
+ * every cell outside the grid counts as blocked, without it cells outside are free and contribute nothing.  The output holds c where
+ * c <= p_max and VHP_CLEARANCE_FAR elsewhere: a blocked cell holds 0, an all-free map without the border flag is VHP_CLEARANCE_FAR
+ * everywhere.  p_max has exactly the domain of vhp_inflate_map's p (a disc 0 .. 4224, a square or a diamond 0 .. 64: a reach of at most
+ * VHP_MAX_INFLATE).  For every p <= p_max, (c > p) is, bit for bit, the map vhp_inflate_map(shape, p, flags) leaves: a robot of squared
+ * radius p fits at a cell exactly when c > p there.  One field therefore answers collision checks for any radius, gives the largest
+ * robot class that fits at a cell, and yields the K configuration-space maps of a fleet from one pass (compare against K values of p on
+ * the device, then vhp_set_maps_device of the K masks).
+ *
+ * uint16_t per cell, nx*ny of them in the layout of vhp_map_occupancy; vhp_maps_clearance writes map first + k of the stack at
+ * out + k*nx*ny (the stack's nx, ny), n maps, and nothing else.  Read from the row-packed copy; the calls change no state.  The host
+ * forms are synchronous and not timed (vhp_last_elapsed_ms keeps what it had); the _device forms are asynchronous on the context's
+ * stream, one kernel launch whatever n.  A null pointer, a d_out not aligned to 2 bytes, a range outside the stack or n < 1 (as
+ * vhp_maps_occupancy), an unknown shape, p_max < 0, a reach above VHP_MAX_INFLATE or an unknown flag (as vhp_inflate_map): VHP_ERR_ARG;
+ * no map (vhp_map_clearance) or no stack (vhp_maps_clearance): VHP_ERR_NO_MAP.  A refused call writes nothing. */
+#define VHP_CLEARANCE_FAR 0xFFFF
+int vhp_map_clearance(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* out);
+int vhp_map_clearance_device(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* d_out);
+int vhp_maps_clearance(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* out);
+int vhp_maps_clearance_device(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* d_out);
 /* Replaces computeVisibility() (solver.cpp:570-696) run on a different environment per source: field i is the sweep from
  * src_xy[2i..2i+1] on map map_idx[i] of the stack, bit for bit what vhp_set_map(that map) + vhp_sweep_batch(VHP_SWEEP_FULL,
  * dtype) gives.  Output layout, zero cells and n_src as in vhp_sweep_batch.  Always the front sweep (vhp_last_sweep_kernel

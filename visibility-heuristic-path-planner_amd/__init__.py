@@ -58,11 +58,13 @@ ABI_SYMBOLS = (
     "vhp_line_of_sight", "vhp_line_of_sight_device",
     "vhp_set_maps_windows", "vhp_set_maps_windows_device", "vhp_maps_occupancy", "vhp_maps_occupancy_device",
     "vhp_inflate_map", "vhp_inflate_maps", "vhp_map_occupancy", "vhp_map_occupancy_device",
+    "vhp_map_clearance", "vhp_map_clearance_device", "vhp_maps_clearance", "vhp_maps_clearance_device",
 )
 
 FOOT_DISC, FOOT_SQUARE, FOOT_DIAMOND = 0, 1, 2   # vhp_footprint
 MAX_INFLATE = 64        # VHP_MAX_INFLATE: the largest reach of a footprint, in cells
 INFLATE_BORDER = 1      # VHP_INFLATE_BORDER: cells outside the grid count as blocked
+CLEARANCE_FAR = 0xFFFF  # VHP_CLEARANCE_FAR: a clearance field's value where no blocked cell lies within p_max
 _FOOT_SHAPES = {"disc": FOOT_DISC, "square": FOOT_SQUARE, "diamond": FOOT_DIAMOND}
 
 
@@ -144,6 +146,10 @@ def load_library():
     lib.vhp_inflate_maps.argtypes = [vp, i32, i32, i32, i32, i32]
     lib.vhp_map_occupancy.argtypes = [vp, vp]
     lib.vhp_map_occupancy_device.argtypes = [vp, vp]
+    lib.vhp_map_clearance.argtypes = [vp, i32, i32, i32, vp]
+    lib.vhp_map_clearance_device.argtypes = [vp, i32, i32, i32, vp]
+    lib.vhp_maps_clearance.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+    lib.vhp_maps_clearance_device.argtypes = [vp, i32, i32, i32, i32, i32, vp]
     lib.vhp_sweep_maps_batch.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_sweep_maps_batch_device.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.vhp_planner_solve.argtypes = [vp, i32, i32, i32, i32, f64, u64, vp, vp, vp, vp, C.POINTER(u32)]
@@ -345,6 +351,39 @@ class Context:
     def map_occupancy_device(self, d_out):
         """Device-resident, asynchronous on the context stream.  d_out is a raw device pointer to ny * nx bytes."""
         self._check(self.lib.vhp_map_occupancy_device(self.h, C.c_void_p(d_out)))
+
+    def map_clearance(self, radius=None, shape="disc", p=None, border=False):
+        """vhp_map_clearance: the clearance field of the map of set_map as uint16 [ny, nx] -- per cell the smallest footprint
+        parameter at which inflate_map would block it (a disc: the squared distance to the nearest blocked cell; a square or a
+        diamond: that distance in their metric), 0 on a blocked cell, CLEARANCE_FAR where it is above p_max.  The footprint as in
+        `footprint` names p_max (one of radius and p; a reach of at most MAX_INFLATE cells); cells outside the grid are free, or
+        blocked with border=True.  (field > p) is map_occupancy() after inflate_map(p=p) for every p <= p_max: a robot of squared
+        radius p fits at a cell exactly when field > p there.  Changes no state."""
+        s, p = footprint(radius, shape, p)
+        out = np.empty((self.ny, self.nx), np.uint16)
+        self._check(self.lib.vhp_map_clearance(self.h, s, p, INFLATE_BORDER if border else 0, _ptr(out)))
+        return out
+
+    def map_clearance_device(self, d_out, radius=None, shape="disc", p=None, border=False):
+        """Device-resident, asynchronous on the context stream.  d_out is a raw device pointer to ny * nx uint16."""
+        s, p = footprint(radius, shape, p)
+        self._check(self.lib.vhp_map_clearance_device(self.h, s, p, INFLATE_BORDER if border else 0, C.c_void_p(d_out)))
+
+    def maps_clearance(self, first=0, n=None, radius=None, shape="disc", p=None, border=False):
+        """vhp_maps_clearance: the same for maps first .. first + n - 1 of the stack (default: all from `first`), every map by
+        itself, as uint16 [n, maps_ny, maps_nx]."""
+        s, p = footprint(radius, shape, p)
+        n = self.n_maps - int(first) if n is None else int(n)
+        out = np.empty((max(n, 0), self.maps_ny, self.maps_nx), np.uint16)
+        self._check(self.lib.vhp_maps_clearance(self.h, int(first), n, s, p, INFLATE_BORDER if border else 0, _ptr(out)))
+        return out
+
+    def maps_clearance_device(self, d_out, first=0, n=None, radius=None, shape="disc", p=None, border=False):
+        """Device-resident, asynchronous on the context stream, one launch whatever n.  d_out is a raw device pointer to
+        n * maps_ny * maps_nx uint16; map first + k goes to element k * maps_ny * maps_nx."""
+        s, p = footprint(radius, shape, p)
+        n = self.n_maps - int(first) if n is None else int(n)
+        self._check(self.lib.vhp_maps_clearance_device(self.h, int(first), n, s, p, INFLATE_BORDER if border else 0, C.c_void_p(d_out)))
 
     def sweep_windows(self, sources, radius, dtype=F64):
         """Range-limited sweeps around many sources of the map of set_map: sets windows of side 2 * radius + 1 with origin

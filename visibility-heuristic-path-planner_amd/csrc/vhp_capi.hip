@@ -95,6 +95,7 @@ struct vhp_ctx {
   vhp::PackedMaps maps;
   vhp::DevBuf<int32_t> d_map_idx;   // host-buffer form's slice of map indices (grow-only)
   vhp::DevBuf<uint64_t> d_inflate;  // vhp_inflate_map / vhp_inflate_maps: the inflated packed copies before they replace the old ones (grow-only)
+  vhp::DevBuf<uint16_t> d_clearance;  // vhp_map_clearance / vhp_maps_clearance: the host forms' field before it is copied out (grow-only)
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
   vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
@@ -1152,6 +1153,76 @@ int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out) {
   VHP_HIP(hipMemcpyAsync(occ_out, ctx->d_out.get(), cells, hipMemcpyDeviceToHost, ctx->stream));
   VHP_HIP(hipStreamSynchronize(ctx->stream));
   return VHP_OK;
+}
+
+// The clearance field of n maps of one packed stack -- rows: map 0's row-packed copy -- at d_out: one launch (vhp_clearance_stack).
+static int clearance_launch(vhp_ctx* ctx, const uint64_t* rows, int n, int nx, int ny, int wpr, int shape, int p_max, int reach, int flags,
+                            uint16_t* d_out) {
+  const long long tiles = (long long)(wpr - 2) * ((ny + vhp::kClearanceTileRows - 1) / vhp::kClearanceTileRows);
+  hipLaunchKernelGGL(vhp::vhp_clearance_stack, dim3((unsigned)tiles, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream, rows, d_out, n, nx, ny, wpr,
+                     shape, p_max, reach, flags & VHP_INFLATE_BORDER);
+  VHP_HIP(hipGetLastError());
+  return VHP_OK;
+}
+
+// What the four clearance calls check, in the order of the header: the pointer, the map or stack (single: the map of vhp_set_map),
+// the range, the footprint and the flags.  *m is the packed maps to read, *reach the footprint's.
+static int clearance_check(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, const uint16_t* out, bool device,
+                           const vhp::PackedMaps** m, int* reach) {
+  static_assert(vhp::kClearanceFar == VHP_CLEARANCE_FAR, "vhp_clearance.hpp and vhp.h disagree on the far value");
+  if (!ctx || !out) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
+  *m = single ? &ctx->map : &ctx->maps;
+  if (!(*m)->rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + (single ? ": no map set" : ": no maps set"));
+  if (!single && (n < 1 || first < 0 || first >= (*m)->n || n > (*m)->n - first)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": maps outside the stack");
+  vhp::InflateTable t;
+  if (const int rc = inflate_footprint(ctx, who, shape, p_max, flags, &t); rc != VHP_OK) return rc;
+  if (device && (reinterpret_cast<uintptr_t>(out) & 1) != 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": d_out is not aligned to 2 bytes");
+  *reach = t.reach;
+  return VHP_OK;
+}
+
+static int clearance_device(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, uint16_t* d_out) {
+  const vhp::PackedMaps* m;
+  int reach;
+  if (const int rc = clearance_check(ctx, who, single, first, n, shape, p_max, flags, d_out, true, &m, &reach); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  return clearance_launch(ctx, m->rows.get() + (size_t)first * m->ny * m->wpr, n, m->nx, m->ny, m->wpr, shape, p_max, reach, flags, d_out);
+}
+
+// The host forms: slices of at most ~1 GiB of field through d_clearance, as vhp_maps_occupancy's bytes (one slice, and one launch,
+// for anything smaller)
+static int clearance_host(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, uint16_t* out) {
+  const vhp::PackedMaps* m;
+  int reach;
+  if (const int rc = clearance_check(ctx, who, single, first, n, shape, p_max, flags, out, false, &m, &reach); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  const size_t cells = (size_t)m->nx * m->ny;
+  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 29) / cells));
+  const hipError_t e = ctx->d_clearance.grow((size_t)slice * cells * 2);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
+  for (int k0 = 0; k0 < n; k0 += slice) {
+    const int nk = std::min(slice, n - k0);
+    if (const int rc = clearance_launch(ctx, m->rows.get() + (size_t)(first + k0) * m->ny * m->wpr, nk, m->nx, m->ny, m->wpr, shape, p_max, reach, flags,
+                                        ctx->d_clearance.get());
+        rc != VHP_OK)
+      return rc;
+    VHP_HIP(hipMemcpyAsync(out + (size_t)k0 * cells, ctx->d_clearance.get(), (size_t)nk * cells * 2, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return VHP_OK;
+}
+
+int vhp_map_clearance(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* out) {
+  return clearance_host(ctx, "vhp_map_clearance", true, 0, 1, shape, p_max, flags, out);
+}
+int vhp_map_clearance_device(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* d_out) {
+  return clearance_device(ctx, "vhp_map_clearance_device", true, 0, 1, shape, p_max, flags, d_out);
+}
+int vhp_maps_clearance(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* out) {
+  return clearance_host(ctx, "vhp_maps_clearance", false, first, n, shape, p_max, flags, out);
+}
+int vhp_maps_clearance_device(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* d_out) {
+  return clearance_device(ctx, "vhp_maps_clearance_device", false, first, n, shape, p_max, flags, d_out);
 }
 
 static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out,

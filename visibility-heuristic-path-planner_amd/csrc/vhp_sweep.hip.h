@@ -1443,3 +1443,5 @@ __global__ void __launch_bounds__(256) vhp_inflate_stack(const uint64_t* __restr
 }
 
 }  // namespace vhp
+
+#include "vhp_clearance.hip.h"  // the clearance field of the packed maps: a kernel of its own file
