@@ -14,7 +14,7 @@
 
 namespace {
 
-// The layout of vhp_pack_rows / vhp_pack_cols: wpr = ceil(nx / 64) + 2 words a row, the first and the last a zero pad.
+// The layout of vhp_pack_rows_stack / vhp_pack_cols_stack: wpr = ceil(nx / 64) + 2 words a row, the first and the last a zero pad.
 struct HostMaps {
   int nx, ny, wpr, wpc;
   std::vector<uint64_t> rows, cols;

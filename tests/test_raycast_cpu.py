@@ -1,6 +1,6 @@
 """Ray casting for batches of sources, without a GPU: the shared ray walk of csrc/vhp_raycast.hpp -- what the field kernel and the
-line-of-sight kernel call -- run by tests/raycast_driver.cpp over maps it packs on the host in the layout of vhp_pack_rows / vhp_pack_cols,
-and held byte for byte to oracle.raycast_all; the launch plan's coverage; the step count of a ray against the reference's own loop; the
+line-of-sight kernel call -- run by tests/raycast_driver.cpp over maps it packs on the host in the layout of vhp_pack_rows_stack /
+vhp_pack_cols_stack, and held byte for byte to oracle.raycast_all; the launch plan's coverage; the step count of a ray against the reference's own loop; the
 new symbols in the header and the binding.  The driver is built plain and under the address and undefined-behaviour sanitizers, and
 every check runs through both."""
 import os

@@ -21,6 +21,7 @@
 #include "vhp_batch_launch.h"
 #include "vhp_choice.hpp"
 #include "vhp_sweep.hip.h"
+#include "vhp_maps.hip.h"
 #include "vhp_planner.hip.h"
 #include "vhp_planner_batch.hip.h"
 #include "vhp_paths.hip.h"
@@ -95,7 +96,6 @@ struct vhp_ctx {
   vhp::PackedMaps maps;
   vhp::DevBuf<int32_t> d_map_idx;   // host-buffer form's slice of map indices (grow-only)
   vhp::DevBuf<uint64_t> d_inflate;  // vhp_inflate_map / vhp_inflate_maps: the inflated packed copies before they replace the old ones (grow-only)
-  vhp::DevBuf<uint16_t> d_clearance;  // vhp_map_clearance / vhp_maps_clearance: the host forms' field before it is copied out (grow-only)
   vhp::BatchState maps_batch;       // the planner batch on the stack (vhp_planner_solve_maps_batch): apart from `batch` and pl
   vhp::PathsScratch paths;          // scratch and staging of the path calls (vhp_planner_path, vhp_planner_[maps_]batch_paths)
   vhp::TreeScratch tree;            // tables and staging of the tree calls (vhp_planner_length_fields, vhp_planner_goal_paths)
@@ -164,7 +164,7 @@ vhp::DevMap dev_map(const vhp::PackedMaps& p) {
 }
 
 vhp::MapStack maps_stack(const vhp::PackedMaps& p, const int32_t* d_map_idx) {
-  return {d_map_idx, p.n, (long long)p.ny * p.wpr, (long long)p.nx * p.wpc};
+  return {d_map_idx, p.n, vhp::map_rows(p, 1) - vhp::map_rows(p, 0), vhp::map_cols(p, 1) - vhp::map_cols(p, 0)};
 }
 
 void free_map(vhp_ctx* c) {
@@ -181,18 +181,6 @@ void free_map(vhp_ctx* c) {
 void free_maps(vhp_ctx* c) {
   c->maps = vhp::PackedMaps{};
   vhp::batch_free(c->maps_batch);
-}
-
-// RN(1/k) for k = 1 .. max(nx, ny) + kRecipPad, and 0 for k = 0
-std::vector<double> recip_table(int nx, int ny) {
-  const int nrec = std::max(nx, ny) + 1 + vhp::kRecipPad;
-  std::vector<double> recip(nrec);
-  recip[0] = 0.0;
-  for (int k = 1; k < nrec; ++k) {
-    volatile double d = (double)k;
-    recip[k] = 1.0 / d;  // correctly rounded IEEE division on the host
-  }
-  return recip;
 }
 
 // How an internal launch writes its fields and whether vhp_timing times it.  The entry point passes it down; nothing parks it on the
@@ -433,11 +421,40 @@ hipError_t launch_maps_sweep(vhp_ctx* c, const int32_t* d_src, const int32_t* d_
   return launch_fronts<OutT>(c, c->maps, d_src, n_src, d_out, p, o, &st);
 }
 
-// The host-buffer sweeps: the sources checked on the host, then slices of at most ~1 GiB of output through the context's
-// scratch (d_src / d_out) -- copy in, launch(n), copy out, synchronise.
-template <typename Launch>
-int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t field, void* out_host, Launch launch);
+// What goes to the host through the context's scratch goes in slices of at most ~1 GiB: so many of n items of item_bytes each
+int slice_items(int n, size_t item_bytes) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / item_bytes)); }
 
+// n items to out_host through the output scratch, slice by slice: produce(k0, nk, d) enqueues items k0 .. k0+nk-1 at d, then copy
+// out, synchronise.  (The caller is on the context's device.)
+template <typename Produce>
+int copy_out_slices(vhp_ctx* ctx, const char* who, int n, size_t item_bytes, void* out_host, Produce produce) {
+  const int slice = slice_items(n, item_bytes);
+  const hipError_t e = ctx->d_out.grow((size_t)slice * item_bytes);
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
+  for (int k0 = 0; k0 < n; k0 += slice) {
+    const int nk = std::min(slice, n - k0);
+    if (const int rc = produce(k0, nk, ctx->d_out.get()); rc != VHP_OK) return rc;
+    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)k0 * item_bytes, ctx->d_out.get(), (size_t)nk * item_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VHP_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return VHP_OK;
+}
+
+// The host-buffer sweeps' slices of fields of `field` bytes: a slice's sources copied to d_src, launch(s0, n) sweeps them -- sources
+// s0 .. s0+n-1 -- into d_out.
+template <typename Launch>
+int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t field, void* out_host, Launch launch) {
+  if (n_src == 0) return VHP_OK;
+  VHP_ON_DEVICE(ctx);
+  const hipError_t e = ctx->d_src.grow((size_t)slice_items(n_src, field) * 2 * sizeof(int32_t));
+  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
+  return copy_out_slices(ctx, who, n_src, field, out_host, [&](int s0, int n, void*) -> int {
+    VHP_HIP(hipMemcpyAsync(ctx->d_src.get(), src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return launch(s0, n);
+  });
+}
+
+// ... of vhp_sweep_batch: the sources checked on the host first
 template <typename Launch>
 int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t esz, void* out_host, Launch launch) {
   for (int s = 0; s < n_src; ++s)
@@ -446,129 +463,78 @@ int stage_batch(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src,
   return stage_slices(ctx, who, src_xy, n_src, (size_t)ctx->map.nx * ctx->map.ny * esz, out_host, [&](int, int n) { return launch(n); });
 }
 
-// ... the slices of fields of `field` bytes: launch(s0, n) sweeps sources s0 .. s0+n-1, staged at d_src
-template <typename Launch>
-int stage_slices(vhp_ctx* ctx, const char* who, const int32_t* src_xy, int n_src, size_t field, void* out_host, Launch launch) {
-  if (n_src == 0) return VHP_OK;
-  VHP_ON_DEVICE(ctx);
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_src, ((size_t)1 << 30) / field));
-  hipError_t e = ctx->d_src.grow((size_t)slice * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = ctx->d_out.grow((size_t)slice * field);
+// ... on a stack: the slice's map indices, map_idx[s0 .. s0+n-1], at d_map_idx
+int stage_map_idx(vhp_ctx* ctx, const char* who, const int32_t* map_idx, int s0, int n) {
+  const hipError_t e = ctx->d_map_idx.grow((size_t)n * sizeof(int32_t));
   if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
-  for (int s0 = 0; s0 < n_src; s0 += slice) {
-    const int n = std::min(slice, n_src - s0);
-    VHP_HIP(hipMemcpyAsync(ctx->d_src.get(), src_xy + 2 * (size_t)s0, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = launch(s0, n);
-    if (rc != VHP_OK) return rc;
-    VHP_HIP(hipMemcpyAsync(static_cast<char*>(out_host) + (size_t)s0 * field, ctx->d_out.get(), (size_t)n * field, hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  VHP_HIP(hipMemcpyAsync(ctx->d_map_idx.get(), map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   return VHP_OK;
 }
 
-// The packed copies of n maps of nx x ny into m: allocated and zeroed, packed by pack(wpr, wpc, row_blocks, col_blocks) -- the caller's
-// kernels on the context's stream, blocks of 256 threads for one map's words --, the reciprocal table uploaded, and the sizes recorded
-// once all of it is on the device.  m comes in empty; on failure the caller drops what was built.
-template <typename Pack>
-int build_packed(vhp_ctx* ctx, vhp::PackedMaps& m, int n, int nx, int ny, Pack pack) {
-  const int wpr = (nx + 63) / 64 + 2, wpc = (ny + 63) / 64 + 2;
-  const size_t rows_words = (size_t)n * ny * wpr, cols_words = (size_t)n * nx * wpc;
-  VHP_HIP(m.rows.grow(rows_words * 8));
-  VHP_HIP(m.cols.grow(cols_words * 8));
-  VHP_HIP(hipMemsetAsync(m.rows.get(), 0, rows_words * 8, ctx->stream));
-  VHP_HIP(hipMemsetAsync(m.cols.get(), 0, cols_words * 8, ctx->stream));
-  const unsigned row_blocks = (unsigned)(((long long)(wpr - 2) * ny * 64 + 255) / 256), col_blocks = (unsigned)(((long long)(wpc - 2) * nx * 64 + 255) / 256);
-  if (const int rc = pack(wpr, wpc, row_blocks, col_blocks); rc != VHP_OK) return rc;
-  const std::vector<double> recip = recip_table(nx, ny);
-  VHP_HIP(m.recip.grow(recip.size() * sizeof(double)));
-  VHP_HIP(hipMemcpyAsync(m.recip.get(), recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VHP_HIP(hipStreamSynchronize(ctx->stream));
-  m.n = n; m.nx = nx; m.ny = ny; m.wpr = wpr; m.wpc = wpc;
+// ... and afterwards: a source the kernels rejected (vhp_raycast.hpp raycast_source_ok; map_idx null: the single map) leaves its field
+// unwritten -- zero here, not what the scratch held
+void zero_rejected_fields(const vhp::PackedMaps& m, const int32_t* src_xy, const int32_t* map_idx, int n_src, void* out_host, size_t field) {
+  for (int i = 0; i < n_src; ++i)
+    if (!vhp::raycast_source_ok(src_xy, map_idx, i, m.nx, m.ny, m.n)) std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
+}
+
+int hip_rc(vhp_ctx* ctx, const char* what, hipError_t e) {
+  return e == hipSuccess ? VHP_OK : fail(ctx, VHP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The device copy of the host array of `count` elements at src, in `staged` for this call only -- or src itself, already there
+template <typename T>
+int device_copy(vhp_ctx* ctx, const T* src, size_t count, bool from_device, vhp::DevBuf<T>& staged, const T** d) {
+  *d = src;
+  if (from_device) return VHP_OK;
+  VHP_HIP(staged.grow(count * sizeof(T)));
+  VHP_HIP(hipMemcpyAsync(staged.get(), src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  *d = staged.get();
   return VHP_OK;
 }
 
 // The single map from d_occ, with its diagonal maps where the latency sweep takes the grid.
 int finish_set_map(vhp_ctx* ctx, int nx, int ny) {
-  vhp::PackedMaps& m = ctx->map;
-  return build_packed(ctx, m, 1, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
-    hipLaunchKernelGGL(vhp::vhp_pack_rows, dim3(row_blocks), dim3(256), 0, ctx->stream, ctx->d_occ.get(), m.rows.get(), nx, ny, wpr);
-    VHP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vhp::vhp_pack_cols, dim3(col_blocks), dim3(256), 0, ctx->stream, ctx->d_occ.get(), m.cols.get(), nx, ny, wpc);
-    VHP_HIP(hipGetLastError());
-    if (vhp::lat_supported(nx, ny)) {
-      const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
-      VHP_HIP(m.dmap.grow(bytes));
-      VHP_HIP(hipMemsetAsync(m.dmap.get(), 0, bytes, ctx->stream));
-      VHP_HIP(vhp::lat_pack_diag_maps(ctx->d_occ.get(), nx, ny, m.dmap.get(), ctx->stream));
-    }
-    return VHP_OK;
-  });
+  return hip_rc(ctx, "packing the map", vhp::maps_build(ctx->map, 1, nx, ny, ctx->stream, [&](vhp::PackedMaps& m) {
+    hipError_t e = vhp::maps_pack(m, ctx->d_occ.get(), ctx->stream);
+    if (e != hipSuccess || !vhp::lat_supported(nx, ny)) return e;
+    const size_t bytes = vhp::lat_diag_map_bytes(nx, ny);
+    e = m.dmap.grow(bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(m.dmap.get(), 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = vhp::lat_pack_diag_maps(ctx->d_occ.get(), nx, ny, m.dmap.get(), ctx->stream);
+    return e;
+  }));
+}
+
+// The single map replaced by the nx x ny map whose bytes fill(d_occ) enqueues: the stream drained, the old map and all that hangs on
+// it dropped, then the new one whole -- or no map, not half of one.
+template <typename Fill>
+int replace_map(vhp_ctx* ctx, int nx, int ny, Fill fill) {
+  VHP_HIP(hipStreamSynchronize(ctx->stream));
+  free_map(ctx);
+  ctx->opt_field_stride = 0;  // (a stride belongs to a grid: one left over from a smaller grid would make the fields overlap)
+  VHP_HIP(ctx->d_occ.grow((size_t)nx * ny));
+  int rc = fill(ctx->d_occ.get());
+  if (rc == VHP_OK) rc = finish_set_map(ctx, nx, ny);
+  if (rc != VHP_OK) free_map(ctx);
+  return rc;
 }
 
 // The stack of vhp_set_maps from the n_maps uint8 maps at src (host or device): both packed copies of every map, one launch each.
 int build_maps(vhp_ctx* ctx, const uint8_t* src, int n_maps, int nx, int ny, bool from_device) {
-  vhp::DevBuf<uint8_t> staged;  // the host maps' device copy, for the packing only
-  const size_t cells = (size_t)n_maps * nx * ny;
-  const uint8_t* d_occ = src;
-  if (!from_device) {
-    VHP_HIP(staged.grow(cells));
-    VHP_HIP(hipMemcpyAsync(staged.get(), src, cells, hipMemcpyHostToDevice, ctx->stream));
-    d_occ = staged.get();
-  }
-  vhp::PackedMaps& m = ctx->maps;
-  return build_packed(ctx, m, n_maps, nx, ny, [&](int wpr, int wpc, unsigned row_blocks, unsigned col_blocks) -> int {
-    const unsigned gy = (unsigned)std::min(n_maps, 65535);  // (the kernels step through more maps than that)
-    hipLaunchKernelGGL(vhp::vhp_pack_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.rows.get(), n_maps, nx, ny, wpr);
-    VHP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vhp::vhp_pack_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, d_occ, m.cols.get(), n_maps, nx, ny, wpc);
-    VHP_HIP(hipGetLastError());
-    return VHP_OK;
-  });
+  vhp::DevBuf<uint8_t> staged;
+  const uint8_t* d_occ;
+  if (const int rc = device_copy(ctx, src, (size_t)n_maps * nx * ny, from_device, staged, &d_occ); rc != VHP_OK) return rc;
+  return hip_rc(ctx, "packing the maps", vhp::maps_build(ctx->maps, n_maps, nx, ny, ctx->stream, [&](vhp::PackedMaps& m) { return vhp::maps_pack(m, d_occ, ctx->stream); }));
 }
 
 // The stack of vhp_set_maps_windows: n_win windows of w x h of the single map, cut from its packed copies at the origins at src (host
-// or device) -- one thread per word, one launch per copy.
+// or device).
 int build_windows(vhp_ctx* ctx, const int32_t* src, int n_win, int w, int h, bool from_device) {
-  vhp::DevBuf<int32_t> staged;  // the host origins' device copy, for the cut only
-  const int32_t* d_origin = src;
-  if (!from_device) {
-    VHP_HIP(staged.grow((size_t)n_win * 2 * sizeof(int32_t)));
-    VHP_HIP(hipMemcpyAsync(staged.get(), src, (size_t)n_win * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    d_origin = staged.get();
-  }
-  const vhp::PackedMaps& s = ctx->map;
-  vhp::PackedMaps& m = ctx->maps;
-  return build_packed(ctx, m, n_win, w, h, [&](int wpr, int wpc, unsigned, unsigned) -> int {
-    const unsigned gy = (unsigned)std::min(n_win, 65535);  // (the kernels step through more windows than that)
-    const unsigned row_blocks = (unsigned)(((long long)(wpr - 2) * h + 255) / 256), col_blocks = (unsigned)(((long long)(wpc - 2) * w + 255) / 256);
-    hipLaunchKernelGGL(vhp::vhp_cut_rows_stack, dim3(row_blocks, gy), dim3(256), 0, ctx->stream, s.rows.get(), s.nx, s.ny, s.wpr, d_origin,
-                       m.rows.get(), n_win, w, h, wpr);
-    VHP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vhp::vhp_cut_cols_stack, dim3(col_blocks, gy), dim3(256), 0, ctx->stream, s.cols.get(), s.nx, s.ny, s.wpc, d_origin,
-                       m.cols.get(), n_win, w, h, wpc);
-    VHP_HIP(hipGetLastError());
-    return VHP_OK;
-  });
-}
-
-// Maps first .. first + n - 1 of the stack as bytes at d_out (vhp_maps_occupancy_device: checked by the caller)
-int unpack_maps(vhp_ctx* ctx, int first, int n, uint8_t* d_out) {
-  const vhp::PackedMaps& m = ctx->maps;
-  const unsigned blocks = (unsigned)(((long long)m.nx * m.ny + 255) / 256);
-  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3(blocks, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream,
-                     m.rows.get() + (size_t)first * m.ny * m.wpr, d_out, n, m.nx, m.ny, m.wpr);
-  VHP_HIP(hipGetLastError());
-  return VHP_OK;
-}
-
-// One packed copy of n maps -- `lines` lines of `cells` cells, wpl words each, from src on -- inflated by the footprint t to dst
-// (vhp_inflate_stack: one thread per data word, the pads of dst the caller's).
-int inflate_copy(vhp_ctx* ctx, const uint64_t* src, uint64_t* dst, int n, int lines, int cells, int wpl, const vhp::InflateTable& t, int flags) {
-  const unsigned blocks = (unsigned)(((long long)(wpl - 2) * lines + 255) / 256);
-  hipLaunchKernelGGL(vhp::vhp_inflate_stack, dim3(blocks, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream, src, dst, n, lines, cells, wpl, t,
-                     flags & VHP_INFLATE_BORDER);
-  VHP_HIP(hipGetLastError());
-  return VHP_OK;
+  vhp::DevBuf<int32_t> staged;
+  const int32_t* d_origin;
+  if (const int rc = device_copy(ctx, src, (size_t)n_win * 2, from_device, staged, &d_origin); rc != VHP_OK) return rc;
+  return hip_rc(ctx, "cutting the windows", vhp::maps_build(ctx->maps, n_win, w, h, ctx->stream, [&](vhp::PackedMaps& m) { return vhp::maps_cut(m, ctx->map, d_origin, ctx->stream); }));
 }
 
 // The footprint of vhp_inflate_map / vhp_inflate_maps, or why not
@@ -804,8 +770,8 @@ int raycast_device(vhp_ctx* ctx, const char* who, bool maps, const int32_t* d_sr
   l.occ = packed_occ(m);
   l.d_map_idx = d_map_idx;
   l.n_maps = m.n;
-  l.rows_stride = (long long)m.ny * m.wpr;
-  l.cols_stride = (long long)m.nx * m.wpc;
+  l.rows_stride = vhp::map_rows(m, 1) - vhp::map_rows(m, 0);
+  l.cols_stride = vhp::map_cols(m, 1) - vhp::map_cols(m, 0);
   l.d_err = ctx->d_err.get();
   l.stream = ctx->stream;
   const hipError_t e = vhp::launch_raycast(l);
@@ -824,19 +790,13 @@ int raycast_host(vhp_ctx* ctx, const char* who, bool maps, const int32_t* src_xy
   if (!esz) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   const size_t field = (size_t)m.nx * m.ny * esz;
   int rc = stage_slices(ctx, who, src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
-    if (maps) {
-      const hipError_t e = ctx->d_map_idx.grow((size_t)n * sizeof(int32_t));
-      if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
-      VHP_HIP(hipMemcpyAsync(ctx->d_map_idx.get(), map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (maps)
+      if (const int r = stage_map_idx(ctx, who, map_idx, s0, n); r != VHP_OK) return r;
     return raycast_device(ctx, who, maps, ctx->d_src.get(), maps ? ctx->d_map_idx.get() : nullptr, n, dtype, ctx->d_out.get());
   });
   if (rc != VHP_OK || n_src == 0) return rc;
   rc = vhp_sync(ctx);
-  // (the kernels leave such a field unwritten: zero here, not what the scratch held)
-  for (int i = 0; i < n_src; ++i)
-    if (!vhp::raycast_source_ok(src_xy, maps ? map_idx : nullptr, i, m.nx, m.ny, m.n))
-      std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
+  zero_rejected_fields(m, src_xy, maps ? map_idx : nullptr, n_src, out_host, field);
   return rc;
 }
 
@@ -908,19 +868,12 @@ static int set_map_common(vhp_ctx* ctx, const uint8_t* src, int nx, int ny, bool
   if (!ctx || !src || nx <= 0 || ny <= 0) return fail(ctx, VHP_ERR_ARG, "vhp_set_map: bad argument");
   if (nx > VHP_MAX_SIDE || ny > VHP_MAX_SIDE) return fail(ctx, VHP_ERR_TOO_LARGE, "vhp_set_map: grid side exceeds VHP_MAX_SIDE");
   VHP_ON_DEVICE(ctx);
-  VHP_HIP(hipStreamSynchronize(ctx->stream));
-  free_map(ctx);
-  ctx->opt_field_stride = 0;  // (a stride belongs to a grid: one left over from a smaller grid would make the fields overlap)
   const size_t n = (size_t)nx * ny;
-  VHP_HIP(ctx->d_occ.grow(n));
-  VHP_HIP(hipMemcpyAsync(ctx->d_occ.get(), src, n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-  ctx->h_occ.clear();
-  ctx->pl.h_occ = nullptr;
-  const int rc = finish_set_map(ctx, nx, ny);
-  if (rc != VHP_OK) {  // (nothing half-set: neither the old grid's sides with the new grid's arrays nor a host copy of a map that is not there)
-    free_map(ctx);
-    return rc;
-  }
+  const int rc = replace_map(ctx, nx, ny, [&](uint8_t* d_occ) -> int {
+    VHP_HIP(hipMemcpyAsync(d_occ, src, n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return VHP_OK;
+  });
+  if (rc != VHP_OK) return rc;  // (nothing half-set: neither the old grid's sides with the new grid's arrays nor a host copy of a map that is not there)
   if (!from_device) ctx->h_occ.assign(src, src + n);
   ctx->pl.h_occ = ctx->h_occ.empty() ? nullptr : ctx->h_occ.data();
   return VHP_OK;
@@ -1038,35 +991,31 @@ int vhp_set_maps_windows_device(vhp_ctx* ctx, const int32_t* d_origin_xy, int n_
   return set_maps_windows_common(ctx, d_origin_xy, n_windows, w, h, true);
 }
 
-static int maps_occupancy_check(vhp_ctx* ctx, const char* who, int first, int n, const uint8_t* out) {
-  if (!ctx || !out || n < 1) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
-  if (!ctx->maps.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + ": no maps set");
-  if (first < 0 || first >= ctx->maps.n || n > ctx->maps.n - first) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": maps outside the stack");
+// The packed maps a call reads -- `single`: the map of vhp_set_map, a stack of one; else the stack of vhp_set_maps -- and its maps
+// first .. first+n-1, checked to lie in them.
+static int select_maps(vhp_ctx* ctx, const char* who, bool single, int first, int n, vhp::PackedMaps** m) {
+  *m = single ? &ctx->map : &ctx->maps;
+  if (!(*m)->rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + (single ? ": no map set" : ": no maps set"));
+  if (n < 1 || first < 0 || first >= (*m)->n || n > (*m)->n - first) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": maps outside the stack");
   return VHP_OK;
+}
+
+// The four occupancy calls: the maps' bytes at `out`, on the device or on the host through the scratch
+static int occupancy(vhp_ctx* ctx, const char* who, bool single, int first, int n, uint8_t* out, bool device) {
+  if (!ctx || !out || n < 1) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
+  vhp::PackedMaps* m;
+  if (const int rc = select_maps(ctx, who, single, first, n, &m); rc != VHP_OK) return rc;
+  VHP_ON_DEVICE(ctx);
+  auto unpack = [&](int k0, int nk, void* d) { return hip_rc(ctx, who, vhp::maps_unpack(*m, first + k0, nk, static_cast<uint8_t*>(d), ctx->stream)); };
+  return device ? unpack(0, n, out) : copy_out_slices(ctx, who, n, (size_t)m->nx * m->ny, out, unpack);
 }
 
 int vhp_maps_occupancy_device(vhp_ctx* ctx, int first, int n, uint8_t* d_occ_out) {
-  if (const int rc = maps_occupancy_check(ctx, "vhp_maps_occupancy_device", first, n, d_occ_out); rc != VHP_OK) return rc;
-  VHP_ON_DEVICE(ctx);
-  return unpack_maps(ctx, first, n, d_occ_out);
+  return occupancy(ctx, "vhp_maps_occupancy_device", false, first, n, d_occ_out, true);
 }
-
-int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out) {
-  if (const int rc = maps_occupancy_check(ctx, "vhp_maps_occupancy", first, n, occ_out); rc != VHP_OK) return rc;
-  VHP_ON_DEVICE(ctx);
-  // slices of at most ~1 GiB through the context's scratch, as the host-buffer sweeps' fields (stage_slices)
-  const size_t cells = (size_t)ctx->maps.nx * ctx->maps.ny;
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / cells));
-  const hipError_t e = ctx->d_out.grow((size_t)slice * cells);
-  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_maps_occupancy: scratch: ") + hipGetErrorString(e));
-  for (int k0 = 0; k0 < n; k0 += slice) {
-    const int nk = std::min(slice, n - k0);
-    if (const int rc = unpack_maps(ctx, first + k0, nk, static_cast<uint8_t*>(ctx->d_out.get())); rc != VHP_OK) return rc;
-    VHP_HIP(hipMemcpyAsync(occ_out + (size_t)k0 * cells, ctx->d_out.get(), (size_t)nk * cells, hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return VHP_OK;
-}
+int vhp_maps_occupancy(vhp_ctx* ctx, int first, int n, uint8_t* occ_out) { return occupancy(ctx, "vhp_maps_occupancy", false, first, n, occ_out, false); }
+int vhp_map_occupancy_device(vhp_ctx* ctx, uint8_t* d_occ_out) { return occupancy(ctx, "vhp_map_occupancy_device", true, 0, 1, d_occ_out, true); }
+int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out) { return occupancy(ctx, "vhp_map_occupancy", true, 0, 1, occ_out, false); }
 
 int vhp_inflate_map(vhp_ctx* ctx, int shape, int p, int flags) {
   if (!ctx) return VHP_ERR_ARG;
@@ -1075,43 +1024,36 @@ int vhp_inflate_map(vhp_ctx* ctx, int shape, int p, int flags) {
   if (const int rc = inflate_footprint(ctx, "vhp_inflate_map", shape, p, flags, &t); rc != VHP_OK) return rc;
   VHP_ON_DEVICE(ctx);
   VHP_HIP(hipStreamSynchronize(ctx->stream));
-  // the inflated rows into scratch (their data words: all the unpacking reads), then vhp_set_map_device's route from their bytes
+  // the inflated rows into scratch (their data words: all the unpacking reads) while the old map is there, then the new map from their bytes
   const int nx = ctx->map.nx, ny = ctx->map.ny, wpr = ctx->map.wpr;
   VHP_HIP(ctx->d_inflate.grow((size_t)ny * wpr * 8));
-  if (const int rc = inflate_copy(ctx, ctx->map.rows.get(), ctx->d_inflate.get(), 1, ny, nx, wpr, t, flags); rc != VHP_OK) return rc;
-  VHP_HIP(hipStreamSynchronize(ctx->stream));
-  free_map(ctx);
-  ctx->opt_field_stride = 0;
-  VHP_HIP(ctx->d_occ.grow((size_t)nx * ny));
-  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3((unsigned)(((long long)nx * ny + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->d_inflate.get(),
-                     ctx->d_occ.get(), 1, nx, ny, wpr);
-  int rc = VHP_OK;
-  if (const hipError_t e = hipGetLastError(); e != hipSuccess) rc = fail(ctx, VHP_ERR_HIP, std::string("vhp_inflate_map: unpack: ") + hipGetErrorString(e));
-  if (rc == VHP_OK) rc = finish_set_map(ctx, nx, ny);
-  if (rc != VHP_OK) free_map(ctx);  // (as a failed vhp_set_map: no map, not half of one)
-  return rc;
+  VHP_HIP(vhp::maps_inflate_copy(ctx->map.rows.get(), ctx->d_inflate.get(), 1, ny, nx, wpr, t, flags & VHP_INFLATE_BORDER, ctx->stream));
+  return replace_map(ctx, nx, ny, [&](uint8_t* d_occ) {
+    return hip_rc(ctx, "vhp_inflate_map: unpack", vhp::maps_unpack(ctx->d_inflate.get(), 1, nx, ny, wpr, d_occ, ctx->stream));
+  });
 }
 
 int vhp_inflate_maps(vhp_ctx* ctx, int first, int n, int shape, int p, int flags) {
   if (!ctx) return VHP_ERR_ARG;
-  vhp::PackedMaps& m = ctx->maps;
-  if (!m.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_inflate_maps: no maps set");
-  if (n < 1 || first < 0 || first >= m.n || n > m.n - first) return fail(ctx, VHP_ERR_ARG, "vhp_inflate_maps: maps outside the stack");
+  vhp::PackedMaps* pm;
+  if (const int rc = select_maps(ctx, "vhp_inflate_maps", false, first, n, &pm); rc != VHP_OK) return rc;
+  vhp::PackedMaps& m = *pm;
   vhp::InflateTable t;
   if (const int rc = inflate_footprint(ctx, "vhp_inflate_maps", shape, p, flags, &t); rc != VHP_OK) return rc;
   VHP_ON_DEVICE(ctx);
   // both copies of the range into scratch -- zeroed first: the pads --, then over the range; anything that fails empties the stack
   const size_t row_words = (size_t)n * m.ny * m.wpr, col_words = (size_t)n * m.nx * m.wpc;
-  uint64_t* const rows = m.rows.get() + (size_t)first * m.ny * m.wpr;
-  uint64_t* const cols = m.cols.get() + (size_t)first * m.nx * m.wpc;
+  uint64_t* const rows = vhp::map_rows(m, first);
+  uint64_t* const cols = vhp::map_cols(m, first);
+  const int border = flags & VHP_INFLATE_BORDER;
   const int rc = [&]() -> int {
     VHP_HIP(hipStreamSynchronize(ctx->stream));
     VHP_HIP(ctx->d_inflate.grow((row_words + col_words) * 8));
     uint64_t* const new_rows = ctx->d_inflate.get();
     uint64_t* const new_cols = new_rows + row_words;
     VHP_HIP(hipMemsetAsync(new_rows, 0, (row_words + col_words) * 8, ctx->stream));
-    if (const int r = inflate_copy(ctx, rows, new_rows, n, m.ny, m.nx, m.wpr, t, flags); r != VHP_OK) return r;
-    if (const int r = inflate_copy(ctx, cols, new_cols, n, m.nx, m.ny, m.wpc, t, flags); r != VHP_OK) return r;
+    VHP_HIP(vhp::maps_inflate_copy(rows, new_rows, n, m.ny, m.nx, m.wpr, t, border, ctx->stream));
+    VHP_HIP(vhp::maps_inflate_copy(cols, new_cols, n, m.nx, m.ny, m.wpc, t, border, ctx->stream));
     VHP_HIP(hipMemcpyAsync(rows, new_rows, row_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
     VHP_HIP(hipMemcpyAsync(cols, new_cols, col_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
     VHP_HIP(hipStreamSynchronize(ctx->stream));
@@ -1127,102 +1069,35 @@ int vhp_inflate_maps(vhp_ctx* ctx, int first, int n, int shape, int p, int flags
   return VHP_OK;
 }
 
-static int unpack_map(vhp_ctx* ctx, uint8_t* d_out) {
-  const vhp::PackedMaps& m = ctx->map;
-  hipLaunchKernelGGL(vhp::vhp_unpack_rows_stack, dim3((unsigned)(((long long)m.nx * m.ny + 255) / 256), 1), dim3(256), 0, ctx->stream, m.rows.get(), d_out,
-                     1, m.nx, m.ny, m.wpr);
-  VHP_HIP(hipGetLastError());
-  return VHP_OK;
-}
-
-int vhp_map_occupancy_device(vhp_ctx* ctx, uint8_t* d_occ_out) {
-  if (!ctx || !d_occ_out) return fail(ctx, VHP_ERR_ARG, "vhp_map_occupancy_device: bad argument");
-  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_map_occupancy_device: no map set");
-  VHP_ON_DEVICE(ctx);
-  return unpack_map(ctx, d_occ_out);
-}
-
-int vhp_map_occupancy(vhp_ctx* ctx, uint8_t* occ_out) {
-  if (!ctx || !occ_out) return fail(ctx, VHP_ERR_ARG, "vhp_map_occupancy: bad argument");
-  if (!ctx->map.rows.get()) return fail(ctx, VHP_ERR_NO_MAP, "vhp_map_occupancy: no map set");
-  VHP_ON_DEVICE(ctx);
-  const size_t cells = (size_t)ctx->map.nx * ctx->map.ny;
-  const hipError_t e = ctx->d_out.grow(cells);
-  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_map_occupancy: scratch: ") + hipGetErrorString(e));
-  if (const int rc = unpack_map(ctx, static_cast<uint8_t*>(ctx->d_out.get())); rc != VHP_OK) return rc;
-  VHP_HIP(hipMemcpyAsync(occ_out, ctx->d_out.get(), cells, hipMemcpyDeviceToHost, ctx->stream));
-  VHP_HIP(hipStreamSynchronize(ctx->stream));
-  return VHP_OK;
-}
-
-// The clearance field of n maps of one packed stack -- rows: map 0's row-packed copy -- at d_out: one launch (vhp_clearance_stack).
-static int clearance_launch(vhp_ctx* ctx, const uint64_t* rows, int n, int nx, int ny, int wpr, int shape, int p_max, int reach, int flags,
-                            uint16_t* d_out) {
-  const long long tiles = (long long)(wpr - 2) * ((ny + vhp::kClearanceTileRows - 1) / vhp::kClearanceTileRows);
-  hipLaunchKernelGGL(vhp::vhp_clearance_stack, dim3((unsigned)tiles, (unsigned)std::min(n, 65535)), dim3(256), 0, ctx->stream, rows, d_out, n, nx, ny, wpr,
-                     shape, p_max, reach, flags & VHP_INFLATE_BORDER);
-  VHP_HIP(hipGetLastError());
-  return VHP_OK;
-}
-
-// What the four clearance calls check, in the order of the header: the pointer, the map or stack (single: the map of vhp_set_map),
-// the range, the footprint and the flags.  *m is the packed maps to read, *reach the footprint's.
-static int clearance_check(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, const uint16_t* out, bool device,
-                           const vhp::PackedMaps** m, int* reach) {
+// The four clearance calls.  The checks in the order of the header: the pointer, the map or stack, the range, the flags and the
+// footprint, and for the device forms the pointer's alignment.  The host forms go through the scratch (one slice, and one launch, for
+// anything under ~1 GiB of field).
+static int clearance(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, uint16_t* out, bool device) {
   static_assert(vhp::kClearanceFar == VHP_CLEARANCE_FAR, "vhp_clearance.hpp and vhp.h disagree on the far value");
   if (!ctx || !out) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": bad argument");
-  *m = single ? &ctx->map : &ctx->maps;
-  if (!(*m)->rows.get()) return fail(ctx, VHP_ERR_NO_MAP, std::string(who) + (single ? ": no map set" : ": no maps set"));
-  if (!single && (n < 1 || first < 0 || first >= (*m)->n || n > (*m)->n - first)) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": maps outside the stack");
+  vhp::PackedMaps* m;
+  if (const int rc = select_maps(ctx, who, single, first, n, &m); rc != VHP_OK) return rc;
   vhp::InflateTable t;
   if (const int rc = inflate_footprint(ctx, who, shape, p_max, flags, &t); rc != VHP_OK) return rc;
   if (device && (reinterpret_cast<uintptr_t>(out) & 1) != 0) return fail(ctx, VHP_ERR_ARG, std::string(who) + ": d_out is not aligned to 2 bytes");
-  *reach = t.reach;
-  return VHP_OK;
-}
-
-static int clearance_device(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, uint16_t* d_out) {
-  const vhp::PackedMaps* m;
-  int reach;
-  if (const int rc = clearance_check(ctx, who, single, first, n, shape, p_max, flags, d_out, true, &m, &reach); rc != VHP_OK) return rc;
   VHP_ON_DEVICE(ctx);
-  return clearance_launch(ctx, m->rows.get() + (size_t)first * m->ny * m->wpr, n, m->nx, m->ny, m->wpr, shape, p_max, reach, flags, d_out);
-}
-
-// The host forms: slices of at most ~1 GiB of field through d_clearance, as vhp_maps_occupancy's bytes (one slice, and one launch,
-// for anything smaller)
-static int clearance_host(vhp_ctx* ctx, const char* who, bool single, int first, int n, int shape, int p_max, int flags, uint16_t* out) {
-  const vhp::PackedMaps* m;
-  int reach;
-  if (const int rc = clearance_check(ctx, who, single, first, n, shape, p_max, flags, out, false, &m, &reach); rc != VHP_OK) return rc;
-  VHP_ON_DEVICE(ctx);
-  const size_t cells = (size_t)m->nx * m->ny;
-  const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 29) / cells));
-  const hipError_t e = ctx->d_clearance.grow((size_t)slice * cells * 2);
-  if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string(who) + ": scratch: " + hipGetErrorString(e));
-  for (int k0 = 0; k0 < n; k0 += slice) {
-    const int nk = std::min(slice, n - k0);
-    if (const int rc = clearance_launch(ctx, m->rows.get() + (size_t)(first + k0) * m->ny * m->wpr, nk, m->nx, m->ny, m->wpr, shape, p_max, reach, flags,
-                                        ctx->d_clearance.get());
-        rc != VHP_OK)
-      return rc;
-    VHP_HIP(hipMemcpyAsync(out + (size_t)k0 * cells, ctx->d_clearance.get(), (size_t)nk * cells * 2, hipMemcpyDeviceToHost, ctx->stream));
-    VHP_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return VHP_OK;
+  auto launch = [&](int k0, int nk, void* d) {
+    return hip_rc(ctx, who, vhp::maps_clearance(*m, first + k0, nk, shape, p_max, t.reach, flags & VHP_INFLATE_BORDER, static_cast<uint16_t*>(d), ctx->stream));
+  };
+  return device ? launch(0, n, out) : copy_out_slices(ctx, who, n, (size_t)m->nx * m->ny * 2, out, launch);
 }
 
 int vhp_map_clearance(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* out) {
-  return clearance_host(ctx, "vhp_map_clearance", true, 0, 1, shape, p_max, flags, out);
+  return clearance(ctx, "vhp_map_clearance", true, 0, 1, shape, p_max, flags, out, false);
 }
 int vhp_map_clearance_device(vhp_ctx* ctx, int shape, int p_max, int flags, uint16_t* d_out) {
-  return clearance_device(ctx, "vhp_map_clearance_device", true, 0, 1, shape, p_max, flags, d_out);
+  return clearance(ctx, "vhp_map_clearance_device", true, 0, 1, shape, p_max, flags, d_out, true);
 }
 int vhp_maps_clearance(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* out) {
-  return clearance_host(ctx, "vhp_maps_clearance", false, first, n, shape, p_max, flags, out);
+  return clearance(ctx, "vhp_maps_clearance", false, first, n, shape, p_max, flags, out, false);
 }
 int vhp_maps_clearance_device(vhp_ctx* ctx, int first, int n, int shape, int p_max, int flags, uint16_t* d_out) {
-  return clearance_device(ctx, "vhp_maps_clearance_device", false, first, n, shape, p_max, flags, d_out);
+  return clearance(ctx, "vhp_maps_clearance_device", false, first, n, shape, p_max, flags, d_out, true);
 }
 
 static int sweep_maps_batch_device(vhp_ctx* ctx, const int32_t* d_src_xy, const int32_t* d_map_idx, int n_src, int dtype, void* d_out,
@@ -1254,19 +1129,12 @@ int vhp_sweep_maps_batch(vhp_ctx* ctx, const int32_t* src_xy, const int32_t* map
   if (dtype != VHP_F64 && dtype != VHP_F32) return fail(ctx, VHP_ERR_ARG, "bad dtype");
   const size_t field = (size_t)ctx->maps.nx * ctx->maps.ny * (dtype == VHP_F64 ? 8 : 4);
   int rc = stage_slices(ctx, "vhp_sweep_maps_batch", src_xy, n_src, field, out_host, [&](int s0, int n) -> int {
-    const hipError_t e = ctx->d_map_idx.grow((size_t)n * sizeof(int32_t));
-    if (e != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("vhp_sweep_maps_batch: scratch: ") + hipGetErrorString(e));
-    VHP_HIP(hipMemcpyAsync(ctx->d_map_idx.get(), map_idx + s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (const int r = stage_map_idx(ctx, "vhp_sweep_maps_batch", map_idx, s0, n); r != VHP_OK) return r;
     return sweep_maps_batch_device(ctx, ctx->d_src.get(), ctx->d_map_idx.get(), n, dtype, ctx->d_out.get(), {0, ctx->timing});
   });
   if (rc != VHP_OK || n_src == 0) return rc;
   rc = vhp_sync(ctx);
-  // the sweep leaves a rejected source's field unwritten: zero here, not what the scratch held
-  for (int i = 0; i < n_src; ++i) {
-    const int x = src_xy[2 * i], y = src_xy[2 * i + 1], k = map_idx[i];
-    if (x < 0 || y < 0 || x >= ctx->maps.nx || y >= ctx->maps.ny || k < 0 || k >= ctx->maps.n)
-      std::memset(static_cast<char*>(out_host) + (size_t)i * field, 0, field);
-  }
+  zero_rejected_fields(ctx->maps, src_xy, map_idx, n_src, out_host, field);
   return rc;
 }
 
@@ -1855,10 +1723,10 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     hipError_t eb = vhp::attach_round_scratch(pm, plan.W * 64 * plan.R, 4, ctx->d_bnd);
     if (eb != hipSuccess) return fail(ctx, VHP_ERR_HIP, std::string("scratch: ") + hipGetErrorString(eb));
     // (where the latency sweep does not take a single source: vhp_planner_sweep, as planner_solve launches it)
-    b.front_sweep = [ctx, pm, plan](const vhp::PlannerDev& d, int k) {
-      vhp::DevMap mk = pm;  // (map k of the stack: map 0's packed copies moved by k strides; k is 0 on the single map)
-      mk.rows += (size_t)k * mk.ny * mk.wpr;
-      mk.cols += (size_t)k * mk.nx * mk.wpc;
+    b.front_sweep = [ctx, pm, plan, pk = &m](const vhp::PlannerDev& d, int k) {
+      vhp::DevMap mk = pm;  // (map k of the stack; k is 0 on the single map)
+      mk.rows = vhp::map_rows(*pk, k);
+      mk.cols = vhp::map_cols(*pk, k);
       auto raise_lds = [ctx](const void* fn, size_t bytes) { return raise_lds_limit(ctx, fn, bytes); };
       return vhp::with_sweep_shape(plan.R, plan.multi, [&](auto r, auto mr) {
         return vhp::launch_planner_kernel<r(), mr()>(vhp::vhp_planner_sweep<r(), mr()>, 4, plan.W, raise_lds, ctx->stream, mk, d);
@@ -1866,7 +1734,7 @@ static int solve_batch(vhp_ctx* ctx, bool maps, const int32_t* queries, const in
     };
     ctx->last_kernel = 1;
   }
-  const vhp::BatchStack st{map_idx, m.rows.get(), (long long)m.ny * m.wpr, m.wpr};
+  const vhp::BatchStack st{map_idx, m.rows.get(), vhp::map_rows(m, 1) - vhp::map_rows(m, 0), m.wpr};
   std::string msg;
   const int rc = vhp::planner_solve_batch(b, pm, maps ? nullptr : ctx->d_occ.get(), maps || ctx->h_occ.empty() ? nullptr : ctx->h_occ.data(), ctx->stream,
                                           ctx->ev0, ctx->ev1, queries, thresholds, n_queries, max_iter, G > 0 ? G : 1, status, n_pivots, &msg,

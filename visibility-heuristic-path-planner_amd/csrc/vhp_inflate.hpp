@@ -1,6 +1,6 @@
 // vhp_inflate.hpp -- obstacles grown by a robot's footprint on the packed maps (vhp_inflate_map, vhp_inflate_maps): the footprint as a
 // table of half-widths and one output word of the inflated map, written once for the device and for the host compiler (no HIP types:
-// tests/inflate_driver.cpp builds it with g++).  vhp_sweep.hip.h holds the kernel around it, beside the other packing kernels.
+// tests/inflate_driver.cpp builds it with g++).  vhp_maps.hip.h holds the kernel around it, beside the other packing kernels.
 //
 // A footprint is a set of integer offsets (dx, dy) picked by a shape and one integer p >= 0 (include/vhp.h vhp_footprint): a disc
 // dx^2 + dy^2 <= p, a square max(|dx|, |dy|) <= p, a diamond |dx| + |dy| <= p.  Cell (x, y) of the inflated map is blocked exactly when

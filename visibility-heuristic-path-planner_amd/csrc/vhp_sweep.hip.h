@@ -56,8 +56,6 @@
 
 #include "vhp_devbuf.hip.h"
 #include "vhp_diag.h"
-#include "vhp_inflate.hpp"
-#include "vhp_window.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -1329,119 +1327,4 @@ __global__ void __launch_bounds__(1024) vhp_order_units(const int32_t* __restric
   }
 }
 
-// ---------------------------------------------------------------------------
-// map packing: one wavefront per 64 cells, ballot -> one word
-// ---------------------------------------------------------------------------
-__global__ void vhp_pack_rows(const uint8_t* __restrict__ occ, uint64_t* __restrict__ rows, int nx, int ny, int wpr) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int words = wpr - 2;
-  if (wave >= words * ny) return;
-  const int y = wave / words, w = wave - y * words;
-  const int x = w * 64 + lane;
-  const bool f = x < nx && occ[(size_t)y * nx + x] != 0;
-  const uint64_t b = __ballot(f);
-  if (lane == 0) rows[(size_t)y * wpr + 1 + w] = b;
-}
-
-__global__ void vhp_pack_cols(const uint8_t* __restrict__ occ, uint64_t* __restrict__ cols, int nx, int ny, int wpc) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int words = wpc - 2;
-  if (wave >= words * nx) return;
-  const int x = wave / words, w = wave - x * words;
-  const int y = w * 64 + lane;
-  const bool f = y < ny && occ[(size_t)y * nx + x] != 0;
-  const uint64_t b = __ballot(f);
-  if (lane == 0) cols[(size_t)x * wpc + 1 + w] = b;
-}
-
-// The same for a stack of n_maps maps of nx x ny (map k at occ + k*nx*ny, its words at rows + k*ny*wpr / cols + k*nx*wpc):
-// one launch per copy, blockIdx.y picks the map (stepping by gridDim.y past 65535 maps).
-__global__ void vhp_pack_rows_stack(const uint8_t* __restrict__ occ, uint64_t* __restrict__ rows, int n_maps, int nx, int ny, int wpr) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int words = wpr - 2;
-  if (wave >= words * ny) return;
-  const int y = wave / words, w = wave - y * words;
-  const int x = w * 64 + lane;
-  for (int k = blockIdx.y; k < n_maps; k += gridDim.y) {
-    const bool f = x < nx && occ[(size_t)k * nx * ny + (size_t)y * nx + x] != 0;
-    const uint64_t b = __ballot(f);
-    if (lane == 0) rows[(size_t)k * ny * wpr + (size_t)y * wpr + 1 + w] = b;
-  }
-}
-
-__global__ void vhp_pack_cols_stack(const uint8_t* __restrict__ occ, uint64_t* __restrict__ cols, int n_maps, int nx, int ny, int wpc) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int words = wpc - 2;
-  if (wave >= words * nx) return;
-  const int x = wave / words, w = wave - x * words;
-  const int y = w * 64 + lane;
-  for (int k = blockIdx.y; k < n_maps; k += gridDim.y) {
-    const bool f = y < ny && occ[(size_t)k * nx * ny + (size_t)y * nx + x] != 0;
-    const uint64_t b = __ballot(f);
-    if (lane == 0) cols[(size_t)k * nx * wpc + (size_t)x * wpc + 1 + w] = b;
-  }
-}
-
-// A stack of n_win windows of w x h cut from the packed copies of one nx x ny map (vhp_set_maps_windows): window k starts at the map's
-// cell (origin_xy[2k], origin_xy[2k+1]), any int32.  One thread per data word (vhp_window.hpp window_word), the pads left to the
-// caller's memset; blockIdx.y picks the window as above.  Neighbouring threads read neighbouring words of one source line.
-__global__ void vhp_cut_rows_stack(const uint64_t* __restrict__ src_rows, int nx, int ny, int src_wpr, const int32_t* __restrict__ origin_xy,
-                                   uint64_t* __restrict__ rows, int n_win, int w, int h, int wpr) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int words = wpr - 2;
-  if (t >= words * h) return;
-  const int j = t / words, k = t - j * words;
-  for (int i = blockIdx.y; i < n_win; i += gridDim.y) {
-    const long long y = window_line(origin_xy[2 * i + 1], j, ny);
-    rows[(size_t)i * h * wpr + (size_t)j * wpr + 1 + k] = window_word(y < 0 ? nullptr : src_rows + (size_t)y * src_wpr, nx, origin_xy[2 * i], w, k);
-  }
-}
-
-// ... and the column-packed copy: the same cut along y of the map's columns
-__global__ void vhp_cut_cols_stack(const uint64_t* __restrict__ src_cols, int nx, int ny, int src_wpc, const int32_t* __restrict__ origin_xy,
-                                   uint64_t* __restrict__ cols, int n_win, int w, int h, int wpc) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int words = wpc - 2;
-  if (t >= words * w) return;
-  const int j = t / words, k = t - j * words;
-  for (int i = blockIdx.y; i < n_win; i += gridDim.y) {
-    const long long x = window_line(origin_xy[2 * i], j, nx);
-    cols[(size_t)i * w * wpc + (size_t)j * wpc + 1 + k] = window_word(x < 0 ? nullptr : src_cols + (size_t)x * src_wpc, ny, origin_xy[2 * i + 1], h, k);
-  }
-}
-
-// Maps first .. first + n - 1 of a stack back to one byte per cell (1 = free), from the row-packed copy (vhp_maps_occupancy): one
-// thread per cell of a map, blockIdx.y picks the map as above; rows points at map `first`.
-__global__ void vhp_unpack_rows_stack(const uint64_t* __restrict__ rows, uint8_t* __restrict__ occ, int n, int nx, int ny, int wpr) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nx * ny) return;
-  const int y = c / nx, x = c - y * nx;
-  for (int k = blockIdx.y; k < n; k += gridDim.y)
-    occ[(size_t)k * nx * ny + c] = (rows[(size_t)k * ny * wpr + (size_t)y * wpr + 1 + (x >> 6)] >> (x & 63)) & 1;
-}
-
-// One packed copy of n_maps maps with their obstacles grown by a footprint (vhp_inflate_map, vhp_inflate_maps): map i's `lines` lines
-// of `cells` cells, wpl words each, at src + i * lines * wpl, inflated to the same place of dst -- never src itself: a word is read by
-// up to 129 lines' threads.  The row-packed copy takes (lines, cells, wpl) = (ny, nx, wpr), the column-packed one (nx, ny, wpc): the
-// footprints are symmetric under x <-> y (vhp_inflate.hpp), so one kernel serves both.  One thread per data word, neighbouring
-// threads on neighbouring words of one line, the pads left to the caller; blockIdx.y picks the map as above.  The table is uniform
-// and indexed by the uniform loop counter: it stays in the kernel arguments.
-__global__ void __launch_bounds__(256) vhp_inflate_stack(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, int n_maps, int lines, int cells,
-                                                         int wpl, InflateTable tab, int border) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int words = wpl - 2;
-  if (t >= words * lines) return;
-  const int j = t / words, k = t - j * words;
-  for (int i = blockIdx.y; i < n_maps; i += gridDim.y) {
-    const size_t at = (size_t)i * lines * wpl;
-    dst[at + (size_t)j * wpl + 1 + k] = inflate_word(src + at, wpl, lines, cells, tab, border != 0, j, k);
-  }
-}
-
 }  // namespace vhp
-
-#include "vhp_clearance.hip.h"  // the clearance field of the packed maps: a kernel of its own file

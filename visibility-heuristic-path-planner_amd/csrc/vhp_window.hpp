@@ -1,5 +1,5 @@
 // vhp_window.hpp -- a window of the packed map as packed words (vhp_set_maps_windows): the cut of one output word, written once for the
-// device and for the host compiler (no HIP types: tests/window_driver.cpp builds it with g++).  vhp_sweep.hip.h holds the kernels
+// device and for the host compiler (no HIP types: tests/window_driver.cpp builds it with g++).  vhp_maps.hip.h holds the kernels
 // around it, beside the other packing kernels.
 //
 // A packed line (DevMap::rows: one row, packed along x; DevMap::cols: one column, packed along y) of n cells is (n + 63) / 64 + 2
