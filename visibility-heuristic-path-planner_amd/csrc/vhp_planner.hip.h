@@ -595,7 +595,7 @@ __global__ void __launch_bounds__(kEpilogueThreads) vhp_spec_epilogue(DevMap m, 
         if (NF > 1 && j >= nc) continue;
         if (CLEAN && j < nc - 1 && vv[j][u] != 0.0) field0[(size_t)j * sp.cells + k] = 0.0;
         const int sx = j == 0 ? sx0 : pivot_x((uint32_t)(nb + j)), sy = j == 0 ? sy0 : pivot_y((uint32_t)(nb + j));
-        if ((x == 0 && sx > 0) || (y == 0 && sy > 0)) continue;  // not swept from this pivot
+        if (planner_unswept(sx, sy, x, y)) continue;  // not swept from this pivot
         visited = true;
         const double v = vv[j][u];
         g = fmax(v, g);  // :417-418
@@ -605,7 +605,7 @@ __global__ void __launch_bounds__(kEpilogueThreads) vhp_spec_epilogue(DevMap m, 
       if (g != oo[u]) d.vis_global[k] = g;
       if (lab != ll[u]) d.label[k] = lab;
       if (g >= d.threshold) {  // :424-430
-        const double h = (d.scale * g) + (eval_d_dev(x, y, d.end_x, d.end_y) + eval_d_dev(x, y, pivot_x(lab), pivot_y(lab)));
+        const double h = planner_h(d.scale, g, eval_d_dev(x, y, d.end_x, d.end_y), eval_d_dev(x, y, pivot_x(lab), pivot_y(lab)));
         PlannerKey c;
         c.h = (unsigned long long)__double_as_longlong(h);
         c.rank = push_rank(nx, ny, sx0, sy0, x, y);
@@ -775,7 +775,7 @@ __global__ void vhp_spec_export_local(DevMap m, PlannerDev d, SpecDev sp) {
   const double* f = sp.cache + (size_t)(sp.sc->cur_slot + last) * sp.cells;
   const int sx = sp.sc->slot_key[2 * (sp.sc->cur_slot + last)], sy = sp.sc->slot_key[2 * (sp.sc->cur_slot + last) + 1];
   const int y = (int)(k / m.nx), x = (int)(k - (size_t)y * m.nx);
-  const bool unvisited = (x == 0 && sx > 0) || (y == 0 && sy > 0);
+  const bool unvisited = planner_unswept(sx, sy, x, y);
   d.vis_local[k] = (d.ctl->iters == 0 || unvisited) ? 0.0 : f[k];
 }
 

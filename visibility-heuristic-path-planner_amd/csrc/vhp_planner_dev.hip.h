@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "vhp.h"
+#include "vhp_planner_cell.hpp"  // PlannerKey, key_less, eval_d_dev, planner_unswept, planner_h, push_rank: one cell's part of a step
 
 namespace vhp {
 
@@ -17,12 +18,6 @@ struct PlannerCtl {
   int done;      // loop finished (any reason)
   int status;    // vhp_status of the solve
   int iters;     // planner steps executed
-};
-
-struct PlannerKey {
-  unsigned long long h;     // bits of the heuristic (h >= 0, so the bit pattern orders like the value)
-  unsigned long long rank;  // push order, lower = earlier
-  int x, y;
 };
 
 struct PlannerDev {
@@ -43,30 +38,6 @@ struct PlannerDev {
   int local_uncached;   // the local fields live in uncached device memory: a one-kernel iteration needs no L2 write-back / invalidate between
                         // its sweep and its epilogue (vhp_lat.hip vhp_planner_iteration)
 };
-
-__device__ __forceinline__ bool key_less(const PlannerKey& a, const PlannerKey& b) {
-  return a.h < b.h || (a.h == b.h && a.rank < b.rank);
-}
-
-// eval_d, visibilityBasedSolver.h:112-115: first product in double, second in int
-__device__ __forceinline__ double eval_d_dev(int ax, int ay, int bx, int by) {
-  const int dx = ax - bx, dy = ay - by;
-  return __builtin_sqrt((double)dx * dx + (double)(dy * dy));
-}
-
-// push-order rank of cell (x, y) for the pivot (sx, sy): quadrants in the order Q1..Q4,
-// inside a quadrant the x offset is the outer loop and the y offset the inner one
-// (solver.cpp:392-395 etc.); a cell several quadrants visit counts where it is first pushed.
-__device__ __forceinline__ unsigned long long push_rank(int nx, int ny, int sx, int sy, int x, int y) {
-  const long long dx = x - sx, dy = y - sy;
-  long long q, r;
-  if (dx >= 0 && dy >= 0) { q = 0; r = dx * (ny - sy) + dy; }
-  else if (dx < 0 && dy >= 0) { q = 1; r = (-dx) * (ny - sy) + dy; }
-  else if (dy < 0 && (dx < 0 || (dx == 0 && sx >= 1))) { q = 2; r = (-dx) * (long long)sy + (-dy); }
-  else { q = 3; r = dx * (long long)sy + (-dy); }
-  (void)nx;
-  return ((unsigned long long)q << 40) | (unsigned long long)r;
-}
 
 // The minimum over a whole wavefront (every lane active), in every lane: four DPP steps inside the rows of 16 (pairs, quads, the
 // half-row and the row mirrored), the four rows' results through scalar registers.  (A butterfly of ds_bpermute takes 12 trips through
@@ -187,7 +158,7 @@ __device__ __forceinline__ bool planner_epilogue_body(int nx, int ny, const Plan
       const int y = (int)((unsigned)k / (unsigned)nx), x = (int)((unsigned)k - (unsigned)y * (unsigned)nx);  // (cells < 2^31: VHP_MAX_SIDE^2)
       // column 0 / row 0 are swept only when the pivot lies on them: unvisited cells are
       // neither united, labelled nor pushed
-      if ((x == 0 && sx > 0) || (y == 0 && sy > 0)) continue;
+      if (planner_unswept(sx, sy, x, y)) continue;
       const double v = vv[u];
       const double old = oo[u];
       const double g = fmax(v, old);  // :417-418
@@ -200,7 +171,7 @@ __device__ __forceinline__ bool planner_epilogue_body(int nx, int ny, const Plan
         }
         const int px = lab < (uint32_t)kPivLds ? piv_lds[2 * lab] : d.pivots[2 * lab];
         const int py = lab < (uint32_t)kPivLds ? piv_lds[2 * lab + 1] : d.pivots[2 * lab + 1];
-        const double h = (d.scale * g) + (eval_d_dev(x, y, d.end_x, d.end_y) + eval_d_dev(x, y, px, py));
+        const double h = planner_h(d.scale, g, eval_d_dev(x, y, d.end_x, d.end_y), eval_d_dev(x, y, px, py));
         PlannerKey c;
         c.h = (unsigned long long)__double_as_longlong(h);
         c.rank = push_rank(nx, ny, sx, sy, x, y);
